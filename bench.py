@@ -3,15 +3,19 @@
 point-clouds/sec (fwd+bwd) of PointNet++ SSG classify, B=32 per GPU, N=4096 (BASELINE.json configs[1]).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full              # + roofline, padded leg, CPU baseline
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR  # + the last timed step's outputs as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 A step = one pass of the hot path over one synthetic batch: forward (FPS, ball query, fused gather + MFMA MLP
 stacks, FC head), cross-entropy, backward through every layer, one flat-bucket gradient all-reduce (N>1), one Adam
 step (the reference's loop, /root/reference/PAPC/train.py:102-116).  Inputs are resident in HBM before the timed
-region.  Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events (library-side event pairs on the
-launch stream) around the dominant kernel family over the timed region; `cpu_baseline` times the torch-CPU port of
-the reference's op decomposition (oracle/torch_cpu_reference.py) on the host cores of this box.
+region.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps steps and prints; everything else
+takes --full (the JSON line keeps its keys, with null where a figure was not measured): `roofline` is measured live
+with HIP events (library-side event pairs on the launch stream) around the dominant kernel family; `cpu_baseline`
+times the torch-CPU port of the reference's op decomposition (oracle/torch_cpu_reference.py) on the host's cores;
+`value_padded` times the compacted stack forced padded; the per-step statistics extend to --min-timed-steps steps.
 """
 import argparse
 import ctypes
@@ -171,7 +175,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=32, help="clouds per GPU (BASELINE config: 32)")
     ap.add_argument("--npoints", type=int, default=4096)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the CPU baseline, the roofline of the "
+                    "dominant kernel family (event-profiled passes of their own), the padded-stack leg (`value_padded`), the compacted stack's row "
+                    "fraction and further timed windows up to --min-timed-steps.  Without it a run sets up, warms up, times --steps steps and prints")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                    "(float32): loss, logits [B, 16] and the flat parameter buffer after its optimiser update (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--config", choices=["ssg", "msg_seg", "pfn", "basic"], default="ssg",
                     help="ssg (default) = the headline BASELINE configs[1]; the other single-GPU configs emit the same JSON (bench_configs.py)")
     ap.add_argument("--overlap", dest="overlap", action="store_true", default=True,
@@ -195,19 +204,20 @@ def main():
     ap.add_argument("--eager-sampling", action="store_true", help="(N > 1) rounds 3-4: three graphs per step with the next batch's pyramid enqueued eagerly on a "
                     "high-priority side stream behind the first; default since round 5: two graphs per step (the cut where the tail bucket's all-reduce is "
                     "issued) and the pyramid as a gated hipGraph on the side stream, as at N = 1")
-    ap.add_argument("--profile-all", action="store_true", help="also print per-family kernel times (stderr)")
+    ap.add_argument("--profile-all", action="store_true", help="(--full) also print per-family kernel times (stderr)")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel of the timed steps eagerly instead of "
                     "replaying the captured hipGraph of zero_grad + forward + loss + backward")
     ap.add_argument("--diag-fixed-plan", action="store_true", help="DIAGNOSTIC ONLY (the printed value is NOT the benchmark): reuse one "
                     "precomputed sampling plan in every step, i.e. time the MLP branch alone, to measure what the sampling overlap costs")
-    ap.add_argument("--no-padded-leg", action="store_true", help="skip the second timed region with the compacted SA2 stack forced padded "
+    ap.add_argument("--no-padded-leg", action="store_true", help="(--full) skip the second timed region with the compacted SA2 stack forced padded "
                     "(`value_padded` in the JSON line)")
     ap.add_argument("--require-graph", action="store_true", help="fail instead of falling back to eager launches when the hipGraph capture "
                     "does not succeed (a multi-GPU run must not quietly measure the slow path)")
     ap.add_argument("--batches", type=int, default=4, help="distinct resident batches the steps cycle through (step j trains on batch j mod this; the side "
                     "stream loads and samples batch j + 1 meanwhile): the compacted stack's row count and the sampling pyramid see different clouds")
-    ap.add_argument("--min-timed-steps", type=int, default=50, help="per-step statistics (ms_median / ms_min / ms_p95, device events around every step) are taken "
-                    "over at least this many steps: when --steps is smaller, further windows of --steps steps follow the contract window")
+    ap.add_argument("--min-timed-steps", type=int, default=50, help="(--full) per-step statistics (ms_median / ms_min / ms_p95, device events around every step) are taken "
+                    "over at least this many steps: when --steps is smaller, further windows of --steps steps follow the contract window "
+                    "(without --full they are taken over the --steps steps of the contract window)")
     ap.add_argument("--allow-gate-timeout", action="store_true", help="(tests) do not abort when a device-side gate wait gave up (papc_flag_wait's sticky count)")
     ap.add_argument("--side-events", action="store_true", help="the gated sampling graph ALSO waits for the previous step's end-of-step event before it is replayed "
                     "(ordering of the shared buffers by stream events as well as by the gate).  Off by default since it was measured: the cross-stream wait costs the "
@@ -234,6 +244,8 @@ def main():
     if (args.gpus > 1 or force1) and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus, force1)
     if args.config != "ssg":
+        if args.dump_outputs:
+            raise SystemExit("[bench] --dump-outputs covers the headline workload (--config ssg) only")
         import bench_configs
         return bench_configs.run(args)
 
@@ -362,7 +374,7 @@ def main():
 
     from papc_amd.head import unit_gradient
     ONE = unit_gradient(dev)                    # d(loss)/d(loss), allocated once; seeding with this tensor skips the loss's multiply-by-one launch
-    state = {"plan": None, "ev": None, "last_grad": None}
+    state = {"plan": None, "ev": None, "last_grad": None, "logits": None}
     # every backward here is followed by an optimiser step: the Adam kernel clears the flat gradient bucket behind its update
     # (papc_adam_step_zero_f32), so the step has no clear_grad launch at its head (PAPC_ZERO_IN_ADAM=0: the separate fill)
     ZERO_IN_ADAM = os.environ.get("PAPC_ZERO_IN_ADAM", "1") != "0"
@@ -406,7 +418,7 @@ def main():
         if args.overlap and args.fork == "start":
             nxt()
         tap = {} if use_dist else None
-        loss, _ = model(x, (s1, s2), plan=plan, after_sa2=(nxt if args.overlap and args.fork == "sa2" else None), tap=tap, labels=y)
+        loss, state["logits"] = model(x, (s1, s2), plan=plan, after_sa2=(nxt if args.overlap and args.fork == "sa2" else None), tap=tap, labels=y)
         work = None
         if use_dist and exchange:
             l2 = tap["l2_points"]
@@ -492,10 +504,11 @@ def main():
         tap = {} if use_dist else None
         if args.diag_fixed_plan:
             plan_in, plan_out = graph_state["fixed_plan"], None
-        loss, _ = model(x, (s1, s2), plan=plan_in, tap=tap,
+        loss, logits = model(x, (s1, s2), plan=plan_in, tap=tap,
                         after_sa2=cut if cut is not None else (open_gate if gate_at == "sa2" else ((fork if args.fork == "sa2" else (mark if args.fork in ("sa2late", "sa2end") else None)) if plan_out is not None and not use_dist else None)),
                         after_sa1=open_gate if gate_at == "sa1" else None,
                         after_sa3=open_gate if gate_at == "sa3" else (((fork if args.fork == "sa3" else ((lambda: fork(fork_ev[0])) if args.fork == "sa2late" else None)) if plan_out is not None and not use_dist else None)), labels=y)
+        graph_state["logits"].append(logits)       # (one per captured set, in the order of graph_state["g"]: --dump-outputs)
         if not use_dist:
             if gate_at == "loss":
                 open_gate()
@@ -528,6 +541,7 @@ def main():
         if ZERO_IN_ADAM:
             flat.zero_grad()                       # (the passes ahead of a capture may have ended without an optimiser step)
         torch.cuda.synchronize()
+        graph_state["logits"] = []
         try:
             load_slot(0, cur["j"])                 # the first replayed step (set 0) trains on batch cur["j"]: its inputs and, below, its plan
             x0, _, s10, s20 = unpack(slots[0])
@@ -779,6 +793,7 @@ def main():
         j = cur["j"]
         cur["j"] = j + 1
         g1, g1b, g2 = graph_state["g"][i]
+        state["logits"] = graph_state["logits"][i]
         if split_pyr and graph_state.get("gB"):
             ev = graph_state["evB"][i]
             if ev is not None:
@@ -883,20 +898,24 @@ def main():
     # N = 1: the W warm-up steps, then the family pass, run eagerly ahead of the capture.  N > 1: the passes ahead of the capture are
     # forward + backward only (no collective on the stream about to be captured, see above); the W warm-up steps proper -- gradient
     # exchange + Adam -- follow the capture, on the launch structure that is timed.
+    # Without --full (or --profile-all) the family pass runs unprofiled: its steps train, so every run walks the same weight trajectory.
     loss = None
     pre = (lambda: step_eager(exchange=False)) if use_dist else step
     for _ in range(max(1, args.warmup) if not use_dist else 2):
         loss = pre()
     torch.cuda.synchronize()
-    lib.papc_prof_enable(0x3FF)
-    lib.papc_prof_reset()
+    family_pass = args.full or args.profile_all
+    if family_pass:
+        lib.papc_prof_enable(0x3FF)
+        lib.papc_prof_reset()
     NPROF = 3
     for _ in range(NPROF):
         loss = pre()
     torch.cuda.synchronize()
-    fam = prof_read(lib)
-    lib.papc_prof_enable(0)
-    dominant = max((k for k in fam if k != 9), key=lambda k: fam[k][0])
+    if family_pass:
+        fam = prof_read(lib)
+        lib.papc_prof_enable(0)
+        dominant = max((k for k in fam if k != 9), key=lambda k: fam[k][0])
     if args.profile_all and rank == 0:
         tot = sum(v[0] for v in fam.values())
         for k, (ms, n) in sorted(fam.items(), key=lambda kv: -kv[1][0]):
@@ -918,7 +937,7 @@ def main():
             dist.barrier()
             dist.destroy_process_group()
         return
-    if not use_graph:
+    if not use_graph and args.full:
         lib.papc_prof_enable(1 << dominant)       # eager timed region: event pairs only around the dominant family
         lib.papc_prof_reset()
 
@@ -960,44 +979,50 @@ def main():
                 "steps_timed": n}
 
     def more_windows(step_ms):
-        """further windows of --steps steps until the per-step statistics stand on --min-timed-steps steps (the contract window stays the first)"""
-        while len(step_ms) < args.min_timed_steps and not args.dump_trajectory and not args.diag_stall_ms:
+        """(--full) further windows of --steps steps until the per-step statistics stand on --min-timed-steps steps (the contract window stays the first)"""
+        while args.full and len(step_ms) < args.min_timed_steps and not args.dump_trajectory and not args.diag_stall_ms:
             timed_region(step_ms)
 
     step_ms, step_batch = [], []               # per-step durations (device events) and the batch each step trained on
     elapsed, loss = timed_region(step_ms)
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:           # what the caller of the last timed step receives: its loss and logits, and the weights it updated
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in (("loss", loss), ("logits", state["logits"]), ("params", flat.data)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.detach().float().cpu().numpy())
     more_windows(step_ms)
     if args.dump_trajectory:                      # rank 0 -> FILE, rank r -> FILE.rank<r>.npz (tests: the replicas must stay identical)
         import numpy as np
         np.savez(args.dump_trajectory if rank == 0 else "%s.rank%d.npz" % (args.dump_trajectory, rank), loss=torch.stack(traj).cpu().numpy(), params=flat.data.detach().cpu().numpy(), params0=params0, grad=(state["last_grad"] if state["last_grad"] is not None else flat.grad).detach().cpu().numpy(),
                  graph=np.array(int(use_graph)), overlap=np.array(int(args.overlap)))
-    n_roof = args.steps
-    if use_graph:
-        # kernels inside a replayed graph cannot carry host-visible event pairs: the dominant family's launch durations are
-        # measured on the same kernels, same inputs, launched eagerly for min(K, 20) further steps right after the timed region
-        n_roof = min(args.steps, 20)
-        lib.papc_prof_enable(1 << dominant)
-        lib.papc_prof_reset()
-        for _ in range(n_roof):
-            step_eager()
+    if args.full:
+        n_roof = args.steps
+        if use_graph:
+            # kernels inside a replayed graph cannot carry host-visible event pairs: the dominant family's launch durations are
+            # measured on the same kernels, same inputs, launched eagerly for min(K, 20) further steps right after the timed region
+            n_roof = min(args.steps, 20)
+            lib.papc_prof_enable(1 << dominant)
+            lib.papc_prof_reset()
+            for _ in range(n_roof):
+                step_eager()
+            torch.cuda.synchronize()
+        # what an event pair itself costs: the two markers are barrier packets with a timestamp write each, and a pair around NOTHING already reads
+        # several microseconds -- measured here on the same stream (median of 200 empty pairs) and reported beside the raw figure; `roofline.frac` is
+        # computed on the family's time with that overhead taken off every launch, which is what agrees with rocprofv3's per-kernel durations
+        # (profiles/), `frac_raw_pairs` keeps the uncorrected one.  (Keeping the host a whole step ahead of the device behind a spinning kernel, so
+        # that no pair sees launch latency, was tried first: the family's time did not move -- the overhead is the markers', not the host's.)
+        pair_ms = []
+        for _ in range(200):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(main)
+            e1.record(main)
+            pair_ms.append((e0, e1))
         torch.cuda.synchronize()
-    # what an event pair itself costs: the two markers are barrier packets with a timestamp write each, and a pair around NOTHING already reads
-    # several microseconds -- measured here on the same stream (median of 200 empty pairs) and reported beside the raw figure; `roofline.frac` is
-    # computed on the family's time with that overhead taken off every launch, which is what agrees with rocprofv3's per-kernel durations
-    # (profiles/), `frac_raw_pairs` keeps the uncorrected one.  (Keeping the host a whole step ahead of the device behind a spinning kernel, so
-    # that no pair sees launch latency, was tried first: the family's time did not move -- the overhead is the markers', not the host's.)
-    pair_ms = []
-    for _ in range(200):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(main)
-        e1.record(main)
-        pair_ms.append((e0, e1))
-    torch.cuda.synchronize()
-    pair_ms = sorted(a.elapsed_time(b) for a, b in pair_ms)
-    pair_overhead_ms = pair_ms[len(pair_ms) // 2]
-    dom_ms, dom_n = prof_read(lib)[dominant]
-    lib.papc_prof_enable(0)
+        pair_ms = sorted(a.elapsed_time(b) for a, b in pair_ms)
+        pair_overhead_ms = pair_ms[len(pair_ms) // 2]
+        dom_ms, dom_n = prof_read(lib)[dominant]
+        lib.papc_prof_enable(0)
     assert final_loss == final_loss, "loss is NaN"
 
     # ---- how much of the headline depends on the generator: the compacted SA2 stack (distinct neighbours only, papc_amd/compact.py) pays
@@ -1010,7 +1035,7 @@ def main():
     sa2_key = (B * 128 * 64, (128, 128, 256))
     compact_on = bool(plans_used.get(sa2_key, {}).get("compact"))
     row_fractions = []
-    if compact_on:
+    if compact_on and args.full:
         for k in range(NB):                       # the compacted stack's device-side row count, batch by batch (the step cycles through them)
             xb, _, s1b, s2b = bt(k)
             pl2 = model.plan_sampling(xb, (s1b, s2b))[1]
@@ -1020,7 +1045,7 @@ def main():
             row_fraction = sum(row_fractions) / len(row_fractions)
             rows_sa2 = int(round(row_fraction * B * 128 * 64))
     padded = None
-    if compact_on and not use_dist and not args.diag_fixed_plan and not args.dump_trajectory and not args.no_padded_leg:     # (one process: a second capture behind collectives would trip RCCL's watchdog, see `comm` above)
+    if args.full and compact_on and not use_dist and not args.diag_fixed_plan and not args.dump_trajectory and not args.no_padded_leg:     # (one process: a second capture behind collectives would trip RCCL's watchdog, see `comm` above)
         model.sa2.compact = False                 # forced padded (layers.PointNetSetAbstraction._compact_mode)
         state["plan"], state["ev"] = None, None
         graph_state.update({"g": None, "loss": None, "i": 0})
@@ -1043,9 +1068,8 @@ def main():
                   "graph": graph_state["g"] is not None, "stats": stats_of(ms_p)}
         model.sa2.compact = None
 
-    if rank == 0:
-        ms_per_step = 1e3 * elapsed / args.steps
-        value = world * B * args.steps / elapsed
+    roof = cpu = None
+    if rank == 0 and args.full:
         flop_fixed, byts_fixed = algorithmic_work(B, N).get(dominant, (0.0, 0.0))
         # priced on what the launches process: the path each stack took (papc_sa_mlp_plan) and the compacted stack's device-side row count;
         # the SURVEY 8d figure, fixed across rounds, stays beside it as `frac_fixed_bytes`
@@ -1109,9 +1133,11 @@ def main():
                           "timed region; the overhead of an event pair itself (median of 200 empty pairs on the same stream) is taken off every "
                           "launch, frac_raw_pairs / ms_per_step_raw_pairs keep the uncorrected figures" % n_roof) if use_graph else "HIP event pairs around every launch of the family over the timed region"
 
-        cpu = None
         if world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(N)
+    if rank == 0:
+        ms_per_step = 1e3 * elapsed / args.steps
+        value = world * B * args.steps / elapsed
         out = {
             "metric": "point-clouds/sec (fwd+bwd) PointNet++SSG B=32 N=4096" + (" -- DIAGNOSTIC, sampling excluded: not a benchmark value" if (args.diag_fixed_plan or args.diag_empty_side) else ""),
             "value": round(value, 2), "unit": "point-clouds/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1119,7 +1145,8 @@ def main():
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": "PointNet++SSG classify fwd+bwd+Adam, B=%d clouds/GPU, N=%d (BASELINE configs[1])" % (B, N),
                        "global_batch": world * B, "parallelism": "dp%d" % world, "final_loss": round(final_loss, 4),
-                       "compact_row_fraction": round(row_fraction, 4), "compact_row_fraction_per_batch": [round(f, 4) for f in row_fractions],
+                       "compact_row_fraction": round(row_fraction, 4) if (args.full or not compact_on) else None,
+                       "compact_row_fraction_per_batch": [round(f, 4) for f in row_fractions],
                        "ms_median_per_batch": [round(stats_of([m for m, bi in zip(step_ms, step_batch) if bi == k])["ms_median"], 4) if any(bi == k for bi in step_batch) else None
                                                for k in range(NB)],
                        "clouds_per_s_per_batch": [round(world * B / (1e-3 * stats_of([m for m, bi in zip(step_ms, step_batch) if bi == k])["ms_median"]), 1)
@@ -1129,8 +1156,10 @@ def main():
                        "timing": "value / ms_per_step: wall clock around the first window of --steps steps between barrier + synchronize (max over ranks); ms_median / ms_min / "
                                  "ms_p95: device events around every step (end-of-step event to end-of-step event on the launch stream, rank 0) over steps_timed steps",
                        "gate_timeouts": gate_timeouts[0],
-                       "compact": ("SA2 on its distinct neighbours (auto policy: kept rows %.3f of the padded count on this generator; ShapeNet-like "
-                                   "surfaces keep 0.91-0.99 and stay padded -> `value_padded` is their rate)" % row_fraction) if compact_on else "padded (policy)",
+                       "compact": ((("SA2 on its distinct neighbours (auto policy: kept rows %.3f of the padded count on this generator; ShapeNet-like "
+                                     "surfaces keep 0.91-0.99 and stay padded -> `value_padded` is their rate)" % row_fraction) if args.full else
+                                    "SA2 on its distinct neighbours (auto policy; --full measures the kept-row fraction and `value_padded`)")
+                                   if compact_on else "padded (policy)"),
                        "sampling": ("software-pipelined: batch i+1's FPS + ball-query pyramid runs as a second branch (side stream) of "
                                     "batch i's step, %s; every timed step computes one full pyramid"
                                     % (("a hipGraph of its own on the side stream, gated on the device behind SA2 (papc_flag_set / papc_flag_wait)" if dist_side_graph else "enqueued on the side stream beside the graph replay") if ext_sampling else

@@ -88,6 +88,32 @@ def test_training_run_is_bit_reproducible_at_the_reference_learning_rate(tmp_pat
         assert np.array_equal(r["grad"], a["grad"]), name
 
 
+def test_dump_outputs_are_the_last_timed_step_and_full_adds_the_extra_figures(tmp_path):
+    """--dump-outputs DIR writes what the last timed step computed: its loss (the trajectory's last entry), its logits and the parameters its
+    optimiser update left.  A plain run times exactly --steps steps and leaves the figures --full measures null; a --full run with the same
+    arguments fills them and dumps the same bits (the dump is taken before anything --full adds)."""
+    import json
+    d_plain, d_full = tmp_path / "plain", tmp_path / "full"
+    t, line = _bench(tmp_path, "dump", "1e-3", "--dump-outputs", str(d_plain))
+    out = json.loads(line)
+    assert out["steps"] == out["steps_timed"] == 10
+    assert out["roofline"] is None and out["cpu_baseline"] is None and out["value_padded"] is None
+    got = {k: np.load(str(d_plain / (k + ".npy"))) for k in ("loss", "logits", "params")}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["loss"].shape == () and got["loss"] == t["loss"][-1]
+    assert got["logits"].shape == (32, 16) and np.all(np.isfinite(got["logits"]))
+    assert np.array_equal(got["params"], t["params"])
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--lr", "1e-3",
+                        "--full", "--dump-outputs", str(d_full)], cwd=ROOT, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"),
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    full = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert full["roofline"]["ms_per_step"] > 0 and full["steps_timed"] >= 50
+    assert full["config"]["final_loss"] == out["config"]["final_loss"]
+    for k, v in got.items():
+        assert np.array_equal(np.load(str(d_full / (k + ".npy"))), v), k
+
+
 def test_training_run_on_the_padded_stack_is_bit_reproducible_too(tmp_path):
     """PAPC_COMPACT=0 -- the layout clouds with few padding copies (ShapeNet-like surfaces) keep: since the list builder makes a group's padding
     copies one weighted entry, the padded stack's gather-add backward runs over the point lists as well (compact.LISTS == 2), so this layout has no

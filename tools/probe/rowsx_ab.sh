@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 mkdir -p gpurun_out/rx
 timeout 600 python -m pytest tests/test_gpu_stream.py -q -m gpu -x > gpurun_out/rx/test.log 2>&1; echo "rc=$?" >> gpurun_out/rx/test.log
 for i in 1 2; do for v in 0 1; do
-  PAPC_DW_ROWSX=$v python bench.py --steps 300 --warmup 30 --no-cpu-baseline 2>/dev/null | python -c "
+  PAPC_DW_ROWSX=$v python bench.py --full --steps 300 --warmup 30 --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('rowsx=$v', d['ms_per_step'], d['value'], d['roofline']['ms_per_step'])" >> gpurun_out/rx/ab.log
 done; done
 d=/tmp/prof_rx; rm -rf $d
