@@ -661,6 +661,22 @@ int papc_head_chain_fwd_f32(const papc_head_fc_layer *layers, int n_layers, int 
                             const int64_t *labels, float *loss, float *dlogits, uint32_t *sync, papc_stream_t stream);
 int papc_head_chain_bwd_f32(const papc_head_bwd_job *jobs, int n_jobs, int B, uint32_t *sync, papc_stream_t stream);
 
+/* Per-cloud transform of the T-Net PointNet (classify/pointnet/pointnet_Conv1D.py:85-88, :96-99), csrc/cloud_transform.hip.
+ *   papc_cloud_transform_f32      y[b, n, :] = x[b, n, :] . T[b]: element (b, n, i) of x at x[b*sb + n*sn + i*sc] (the planar [B, 3, N] input
+ *                                 is sb = 3N, sn = 1, sc = N; rows [B*N, 64] are sb = 64N, sn = 64, sc = 1), T[b] the C x C row-major matrix at T + b*ldt (ldt >= C*C),
+ *                                 y [B, N, C] contiguous.  C = 3 or 64 (else PAPC_E_UNSUPPORTED), B <= 65535.
+ *   papc_cloud_transform_bwd_f32  dY [B, N, C] contiguous -> dT [B, C, C] = X[b]^T . dY[b] and (dx non-null) dX[b] = dY[b] . T[b]^T at
+ *                                 dx[b*dsb + n*dsn + i*dsc], added to what dx holds when accumulate != 0.  Two launches: one pass over
+ *                                 dY in chunks of N (dX rows + a partial dT per chunk into `workspace`), one fold of the partials in chunk
+ *                                 order.  No atomics: bit-reproducible.  workspace: papc_cloud_transform_bwd_workspace(B, N, C) bytes.
+ * Plain fp32 arithmetic: each output is a fmaf chain over the reduced index in ascending order (dT: within a chunk). */
+int papc_cloud_transform_f32(const float *x, int64_t sb, int64_t sn, int64_t sc, const float *T, int64_t ldt, int B, int N, int C, float *y,
+                             papc_stream_t stream);
+size_t papc_cloud_transform_bwd_workspace(int B, int N, int C);
+int papc_cloud_transform_bwd_f32(const float *x, int64_t sb, int64_t sn, int64_t sc, const float *T, int64_t ldt, const float *dy, int B, int N, int C,
+                                 float *dx, int64_t dsb, int64_t dsn, int64_t dsc, int accumulate, float *dT, void *workspace,
+                                 size_t workspace_bytes, papc_stream_t stream);
+
 /* Axis-aligned bitmask NMS: nms_gpu of pointpillars/libs/ops/non_max_suppression/nms_gpu.py:130-164 (CUDA twin
  * libs/ops/cc/nms/nms_kernel.cu.cc:38-157), all on the device.  dets [N,5] = (x1, y1, x2, y2, score) fp32, N <= 65536.
  * keep [N] int32 receives the ORIGINAL indices of the kept boxes in descending-score order (ties: higher index first, the

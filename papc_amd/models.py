@@ -2,6 +2,7 @@
 
   PointNet2_SSG_Clas / PointNet2_MSG_Clas  <- /root/reference/PAPC/models/classify/pointnet2/pointnet2.py:6-41, :43-75
   PointNet_Basic_Clas                      <- /root/reference/PAPC/models/classify/pointnet_base/pointnet_base.py:4-47
+  PointNet_Clas (T-Net PointNet)           <- /root/reference/PAPC/models/classify/pointnet/pointnet_Conv1D.py:4-104
   PointNet2_SSG_Seg / PointNet2_MSG_Seg    <- /root/reference/PAPC/models/segment/pointnet2/pointnet2.py:6-52, :54-100
 
 Inputs are ``[B,3,N]`` float32 (``[B,6,N]`` with normals).  Everything runs in libpapc_hip.so, in train AND eval mode, the FC heads included
@@ -222,6 +223,76 @@ class PointNet_Basic_Clas(nn.Module):
                 spec = self.__dict__["_head_spec"] = _head.HeadSpec()
             return _head.plain_head(spec, feat, self.fc[0], self.fc[2], self.fc[4], self.fc[5], training=self.training)      # :26-33, :45 on the head kernels
         return self.fc(feat)                                      # :45
+
+
+def _conv_bn_relu(chans, pool=None):
+    """nn.Sequential([Conv1D, BatchNorm, ReLU] x len(chans) - 1 (+ MaxPool1D(pool))): the holders of one of pointnet_Conv1D.py's stacks, with
+    the source's indices (conv 3i, norm 3i + 1)"""
+    mods = []
+    for i in range(len(chans) - 1):
+        mods += [nn.Conv1d(chans[i], chans[i + 1], 1), nn.BatchNorm1d(chans[i + 1], eps=1e-5), nn.ReLU()]
+    if pool is not None:
+        mods.append(nn.MaxPool1d(pool))
+    return nn.Sequential(*mods)
+
+
+class PointNet_Clas(nn.Module):
+    """PointNet with an input and a feature T-Net (/root/reference/PAPC/models/classify/pointnet/pointnet_Conv1D.py:4-104).
+
+    The five Conv1D + BN + ReLU stacks run as shared-MLP nodes (one group per cloud, K = N; with the max over N where the source pools),
+    the three T-Net / classifier FC blocks on the head kernels (transform.tnet_fc, head.plain_head), the two per-cloud matrix products
+    x . T[b] on csrc/cloud_transform.hip (transform.py).  Containers and indices are the source's, so checkpoint.export_state /
+    import_state exchange .pdparams with it directly.  The source pools with MaxPool1D(max_point): inputs must have N == max_point."""
+
+    def __init__(self, num_classes=16, max_point=2048):
+        super().__init__()
+        self.max_point = int(max_point)
+        self.input_transform_net = _conv_bn_relu([3, 64, 128, 1024], pool=max_point)                      # :7-18
+        self.input_fc = nn.Sequential(nn.Linear(1024, 512), nn.ReLU(), nn.Linear(512, 256), nn.ReLU(), nn.Linear(256, 9))   # :19-28
+        with torch.no_grad():
+            self.input_fc[4].weight.zero_()                                                                  # :25 Assign(zeros)
+            self.input_fc[4].bias.copy_(torch.eye(3).reshape(-1))                                            # :26 Assign(eye(3))
+        self.mlp_1 = _conv_bn_relu([3, 64, 64])                                                              # :29-36
+        self.feature_transform_net = _conv_bn_relu([64, 64, 128, 1024], pool=max_point)                     # :37-49
+        self.feature_fc = nn.Sequential(nn.Linear(1024, 512), nn.ReLU(), nn.Linear(512, 256), nn.ReLU(), nn.Linear(256, 64 * 64))  # :50-56
+        self.mlp_2 = _conv_bn_relu([64, 64, 128, 1024])                                                      # :57-66
+        self.fc = nn.Sequential(nn.Linear(1024, 512), nn.ReLU(), nn.Linear(512, 256), nn.ReLU(), nn.Dropout(p=0.7),
+                                nn.Linear(256, num_classes))                                                 # :68-75
+
+    def _spec(self, name):
+        spec = self.__dict__.get(name)
+        if spec is None:
+            spec = self.__dict__[name] = _head.HeadSpec()
+        return spec
+
+    def _stack(self, seq, B, N, pool, xyz=None, zero=None, x_rows=None):
+        """relu(bn(conv(.))) x layers of ``seq`` on the fused stack: from the planar coordinates (xyz) or from rows [B*N, C] (x_rows);
+        pool: the max over each cloud's N rows -> [B, C_L], else every row -> [B*N, C_L].  The norms are registered layers of the source,
+        so eval() normalises with their running statistics."""
+        convs = [m for m in seq if isinstance(m, nn.Conv1d)]
+        bns = [m for m in seq if isinstance(m, nn.BatchNorm1d)]
+        spec = StackSpec(B, N, 1, N, 0, xyz_first=True, eps=bns[0].eps, momentum=0.9, pool=pool, eval_bn=not self.training)
+        return shared_mlp_max(spec, _bn_buffers(bns), xyz, zero, None, None, _stack_params(convs, bns), x_rows=x_rows)
+
+    def forward(self, inputs):
+        x = torch.as_tensor(inputs).float()                                  # [B,3,N]
+        if not x.is_cuda:
+            raise _lib.PapcError("PointNet_Clas needs CUDA (ROCm) tensors: there is no CPU fallback")
+        B, _, N = x.shape
+        if N != self.max_point:
+            raise _lib.PapcError("PointNet_Clas: the source pools with MaxPool1D(max_point): N = %d points per cloud, max_point = %d" % (N, self.max_point))
+        from .transform import tnet_fc, transform_points, transform_rows
+        g = self._stack(self.input_transform_net, B, N, True, xyz=x.transpose(1, 2), zero=_lib.const_zeros((B, 1, 3), x.device))   # :81-82
+        t_in = tnet_fc(self._spec("_spec_input_fc"), g, self.input_fc).view(B, 3, 3)                   # :83-84
+        pts = transform_points(x, t_in)                                                                # :86-88 -> [B, N, 3]
+        h = self._stack(self.mlp_1, B, N, False, x_rows=pts.view(B * N, 3))                            # :89 -> [B*N, 64]
+        g = self._stack(self.feature_transform_net, B, N, True, x_rows=h)                              # :91-92
+        t_feat = tnet_fc(self._spec("_spec_feature_fc"), g, self.feature_fc).view(B, 64, 64)           # :93-94
+        h = transform_rows(h, t_feat, N)                                                               # :96-99
+        feat = self._stack(self.mlp_2, B, N, True, x_rows=h)                                           # :100-101 -> [B, 1024]
+        if _FUSED_HEAD and _head.plain_usable(feat, self.fc[0], self.fc[2], self.fc[5], self.training):
+            return _head.plain_head(self._spec("_head_spec"), feat, self.fc[0], self.fc[2], self.fc[4], self.fc[5], training=self.training)   # :102
+        return self.fc(feat)                                                                           # :102
 
 
 def Categorical(y, num_class=16):
