@@ -677,6 +677,30 @@ int papc_cloud_transform_bwd_f32(const float *x, int64_t sb, int64_t sn, int64_t
                                  float *dx, int64_t dsb, int64_t dsn, int64_t dsc, int accumulate, float *dT, void *workspace,
                                  size_t workspace_bytes, papc_stream_t stream);
 
+/* First seg_net layer of the PointNet part segmenters (segment/pointnet/pointnet.py:105-107, segment/pointnet_base/pointnet_base.py:32-35),
+ * csrc/cloud_concat.hip: the 1x1 conv over concat([x (Cp ch), tile(g (Cg ch), N)]) without forming the tile.  Rows are point-major, M = B*N,
+ * cloud b owns rows [b*N, (b+1)*N).  w [Cout, Cp + Cg] is the conv weight read in place (leading dimension Cp + Cg); W_p = w[:, :Cp], W_g = w[:, Cp:].
+ *   papc_cloud_concat_conv_f32   y [M, Cout] = x . W_p^T + c[b(m)], c = cvec [B, Cout] = g . W_g^T + bias (bias may be NULL) -- written for the
+ *                                caller (the backward does not need it).  stats_partial (NULL in eval mode): [papc_cloud_concat_conv_parts(B, N), 2, Cout]
+ *                                per-tile sums / sums of squares of y, the layout papc_bn_finalize_f32 takes (n_tiles = that count).
+ *   papc_cloud_concat_conv_bwd_f32  dY formed on the fly from dz [M, Cout] (dense) and this layer's BN constants (mean, invstd, scale, shift,
+ *                                and c1, c2 from papc_bn_bwd_finalize_f32; eval mode: `accumulate | 2` there): dX_p [M, Cp] = dY . W_p at
+ *                                dx + m*ldd (dx may be NULL; added to what it holds when accumulate != 0); dw [Cout, Cp + Cg] whole, in w's layout
+ *                                (dW_p = dY^T . X_p, dW_g = s^T . g); dbias = sum_b s[b] (may be NULL); dg [B, Cg] = s . W_g (may be NULL); s [B, Cout]
+ *                                = per-cloud column sums of dY, into s_out when given, else kept in the workspace.  Three launches: one pass over
+ *                                dY in chunks of 128 rows of one cloud (dX rows and per-chunk partials), a fixed-order fold, the per-cloud tail.
+ *                                No atomics: bit-reproducible.  workspace: papc_cloud_concat_conv_bwd_workspace(B, N, Cp, Cg, Cout) bytes.
+ * Shapes: Cp = 64, Cg in 64..1024 (a multiple of 64), Cout = 512 (else PAPC_E_UNSUPPORTED); B <= 65535, B*N <= 2^30; x / w / dz / y and the
+ * BN constants 16-byte aligned, ldx a multiple of 4.  Products on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation). */
+int papc_cloud_concat_conv_parts(int B, int N);
+int papc_cloud_concat_conv_f32(const float *x, int64_t ldx, const float *g, const float *w, const float *bias, int B, int N, int Cp, int Cg, int Cout,
+                               float *y, float *cvec, float *stats_partial, papc_stream_t stream);
+size_t papc_cloud_concat_conv_bwd_workspace(int B, int N, int Cp, int Cg, int Cout);
+int papc_cloud_concat_conv_bwd_f32(const float *dz, const float *y, const float *mean, const float *invstd, const float *scale, const float *shift,
+                                   const float *c1, const float *c2, const float *x, int64_t ldx, const float *g, const float *w, int B, int N, int Cp,
+                                   int Cg, int Cout, float *dx, int64_t ldd, int accumulate, float *dw, float *dbias, float *dg, float *s_out,
+                                   void *workspace, size_t workspace_bytes, papc_stream_t stream);
+
 /* Axis-aligned bitmask NMS: nms_gpu of pointpillars/libs/ops/non_max_suppression/nms_gpu.py:130-164 (CUDA twin
  * libs/ops/cc/nms/nms_kernel.cu.cc:38-157), all on the device.  dets [N,5] = (x1, y1, x2, y2, score) fp32, N <= 65536.
  * keep [N] int32 receives the ORIGINAL indices of the kept boxes in descending-score order (ties: higher index first, the

@@ -4,8 +4,10 @@ Public surface mirrors the reference:
   papc_amd.functional  <- PAPC/models/layers/pointnet2_basic_layers.py free functions
   papc_amd.layers      <- PointNetSetAbstraction(.Msg)
   papc_amd.pillars     <- PFNLayer / PillarFeatureNet (pointpillars/models/bones/pillars.py)
-  papc_amd.models      <- PointNet2_SSG_Clas / PointNet2_MSG_Clas / PointNet_Basic_Clas / PointNet_Clas (T-Net PointNet)
+  papc_amd.models      <- PointNet2_SSG_Clas / PointNet2_MSG_Clas / PointNet_Basic_Clas / PointNet_Clas (T-Net PointNet),
+                          PointNet2_SSG_Seg / PointNet2_MSG_Seg / PointNet_Seg / PointNet_Basic_Seg
   papc_amd.transform   <- the T-Net PointNet's per-cloud transform x . T[b] and its T-Net FC blocks
+  papc_amd.segment     <- the PointNet segmenters' first seg_net layer over concat([point, tile(global)]) without the tile
 The compute lives in libpapc_hip.so (hand-written HIP, C ABI in include/papc_hip.h).
 """
 __version__ = "0.1.0"

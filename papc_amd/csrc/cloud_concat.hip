@@ -1,0 +1,386 @@
+// cloud_concat.hip -- the first seg_net layer of the PointNet part segmenters, for gfx950.
+//
+// Reference: /root/reference/PAPC/models/segment/pointnet/pointnet.py:105-107 and pointnet_base/pointnet_base.py:32-35:
+//     x = concat([point_feat (Cp ch), tile(global_feat (Cg ch), N)]);  y = Conv1D(Cp + Cg, Cout, 1)(x)
+// The tiled half is the same for every point of a cloud, so with W = [W_p | W_g] (W_p = W[:, :Cp]):
+//     y[b, n, :] = W_p . x[b, n, :] + c[b, :]          c[b, :] = W_g . g[b, :] + bias
+// and, with s[b] = sum_n dY[b, n, :] (the per-cloud column sums of dY):
+//     dW_g = s^T . g    d bias = sum_b s[b]    dg = s . W_g    dX_p = dY . W_p    dW_p = dY^T . X_p
+// No [B*N, Cp + Cg] tile is ever formed; the per-point GEMMs have K = Cp = 64.
+//
+//   forward   cc_cvec_kernel (c, one wave per output, a fixed DPP tree over Cg) and cc_fwd_kernel (128 x 128 tiles of y, plus the
+//             per-tile column sums / sums of squares of y in papc_bn_finalize_f32's [n_tiles][2][Cout] layout).
+//   backward  cc_bwd_kernel: ONE pass over (dz, y) in chunks of 128 rows of one cloud.  dY is formed on the fly from the layer's BN
+//             constants (as every backward kernel of the stack does), a chunk writes its dX rows, its partial dW_p and its partial column
+//             sums to slots of its own; cc_fold_kernel folds them in chunk order; cc_tail_kernel forms dW_g, d bias and dg from s.
+//             No float atomics: two runs are bit-identical.
+// Products: v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation: the PAPC_GEMM_F32 arithmetic of papc_mlp_gemm_f32).  At
+// K = 64 the layer is bound by the [M, Cout] traffic of y and dY, not by the matrix rate.  The small per-cloud products are fmaf chains
+// in ascending index order.  Plain C++ loads and stores only.
+#include "common.h"
+
+namespace papc {
+
+typedef float cc_floatx16 __attribute__((ext_vector_type(16)));
+
+constexpr int CC_T = 256;        // threads of every kernel here (4 waves)
+constexpr int CC_BM = 128;       // rows per tile (forward) / per chunk (backward)
+constexpr int CC_BN = 128;       // output columns per forward tile
+constexpr int CC_CP = 64;        // the point-feature width the kernels are written for
+constexpr int CC_OB = 64;        // output columns per backward column block
+constexpr int CC_LDA = 68;       // LDS pitch (floats) of the float4-read tiles
+constexpr int CC_LDX = 65;       // LDS pitch of the backward x tile (scalar reads)
+
+__device__ __forceinline__ float4 cc_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ void cc_st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
+
+// ---- forward ------------------------------------------------------------------------------------------------------------------------
+// c[b, o] = bias[o] + sum_k W[o, Cp + k] g[b, k]: workgroup (16 outputs, cloud b), wave = 4 outputs, lane = k (mod 64)
+__global__ __launch_bounds__(CC_T) void cc_cvec_kernel(const float *__restrict__ g, const float *__restrict__ w, int64_t ldw, const float *__restrict__ bias,
+                                                       int Cp, int Cg, int Cout, float *__restrict__ cvec)
+{
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const float *gb = g + (int64_t)b * Cg;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int o = blockIdx.x * 16 + wv * 4 + q;
+        const float *wr = w + (int64_t)o * ldw + Cp;
+        float a = 0.f;
+        for (int k = lane; k < Cg; k += 64) a = fmaf(wr[k], gb[k], a);
+        a = wave_sum_f32_to_lane63(a);
+        if (lane == 63) cvec[(int64_t)b * Cout + o] = bias ? a + bias[o] : a;
+    }
+}
+
+// y tile [128 rows, 128 columns] = x . W_p^T + c[b(row)]; 4 waves of 64 x 64 (2 x 2 MFMA blocks); K = 64 staged whole in LDS
+__global__ __launch_bounds__(CC_T) void cc_fwd_kernel(const float *__restrict__ x, int64_t ldx, const float *__restrict__ w, int64_t ldw,
+                                                      const float *__restrict__ cvec, int M, int N, int Cout, float *__restrict__ y,
+                                                      float *__restrict__ stats)
+{
+    __shared__ float xs[CC_BM * CC_LDA];
+    __shared__ float ws[CC_BN * CC_LDA];
+    __shared__ float red[2][CC_BN];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, hi = lane >> 5;
+    const int n0 = blockIdx.x * CC_BN;
+    const int m0 = blockIdx.y * CC_BM;
+    for (int e = tid; e < CC_BM * 16; e += CC_T) {
+        const int r = e >> 4, q = (e & 15) * 4;
+        const int m = m0 + r;
+        cc_st4(&xs[r * CC_LDA + q], m < M ? cc_ld4(x + (int64_t)m * ldx + q) : make_float4(0.f, 0.f, 0.f, 0.f));
+        cc_st4(&ws[r * CC_LDA + q], cc_ld4(w + (int64_t)(n0 + r) * ldw + q));
+    }
+    __syncthreads();
+    const int wm = wv & 1, wn = wv >> 1;
+    cc_floatx16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    // 32x32x2: lane supplies A[row l31][k] and B[k][col l31]; the two k of one instruction are kk + j (hi = 0) and kk + 4 + j (hi = 1)
+#pragma unroll
+    for (int kk = 0; kk < CC_CP; kk += 8) {
+        float4 a[2], bq[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) a[i] = cc_ld4(&xs[(wm * 64 + i * 32 + l31) * CC_LDA + kk + 4 * hi]);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) bq[j] = cc_ld4(&ws[(wn * 64 + j * 32 + l31) * CC_LDA + kk + 4 * hi]);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].x, bq[j].x, acc[i][j], 0, 0, 0);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].y, bq[j].y, acc[i][j], 0, 0, 0);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].z, bq[j].z, acc[i][j], 0, 0, 0);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].w, bq[j].w, acc[i][j], 0, 0, 0);
+            }
+    }
+    // epilogue: C layout col = l31, row = (r & 3) + 8 (r >> 2) + 4 hi.  Rows past M are neither stored nor counted.
+    float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+            if (m < M) {
+                const float *cb = cvec + (int64_t)(m / N) * Cout;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int col = n0 + wn * 64 + j * 32 + l31;
+                    const float v = acc[i][j][r] + cb[col];
+                    y[(int64_t)m * Cout + col] = v;
+                    s1[j] += v;
+                    s2[j] = fmaf(v, v, s2[j]);
+                }
+            }
+        }
+    if (!stats) return;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {       // the two row halves of a lane pair, then the two row halves of the tile (wm), in fixed order
+        s1[j] += __shfl_xor(s1[j], 32);
+        s2[j] += __shfl_xor(s2[j], 32);
+    }
+    if (wm == 1 && hi == 0) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            red[0][wn * 64 + j * 32 + l31] = s1[j];
+            red[1][wn * 64 + j * 32 + l31] = s2[j];
+        }
+    }
+    __syncthreads();
+    if (wm == 0 && hi == 0) {
+        float *sp = stats + (int64_t)blockIdx.y * 2 * Cout;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int cl = wn * 64 + j * 32 + l31;
+            sp[n0 + cl] = s1[j] + red[0][cl];
+            sp[Cout + n0 + cl] = s2[j] + red[1][cl];
+        }
+    }
+}
+
+// ---- backward -----------------------------------------------------------------------------------------------------------------------
+// chunk (blockIdx.x) of cloud b (blockIdx.y): rows n0 .. n0 + 127 of the cloud (fewer in its last chunk).  Per column block of 64 outputs:
+// dY block -> LDS; dX [128, 64] += dY_blk . W_p_blk (wave = 32 rows, 2 MFMA blocks, kept over the column blocks); partial dW_p [64, 64] =
+// dY_blk^T . X (wave = one 32 x 32 block, K = the chunk's rows); partial column sums of dY.
+__global__ __launch_bounds__(CC_T) void cc_bwd_kernel(const float *__restrict__ dz, const float *__restrict__ yv, const float *__restrict__ mean,
+                                                      const float *__restrict__ invstd, const float *__restrict__ scale, const float *__restrict__ shift,
+                                                      const float *__restrict__ c1, const float *__restrict__ c2, const float *__restrict__ x, int64_t ldx,
+                                                      const float *__restrict__ w, int64_t ldw, int N, int Cout, float *dx, int64_t ldd, int accumulate,
+                                                      float *__restrict__ part_w, float *__restrict__ part_s)
+{
+    __shared__ float xs[CC_BM * CC_LDX];
+    __shared__ float gs[CC_BM * CC_LDA];
+    __shared__ float wt[CC_CP * CC_LDA];       // W_p block transposed: wt[k][o]
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, hi = lane >> 5;
+    const int b = blockIdx.y, ch = blockIdx.x, nch = gridDim.x;
+    const int n0 = ch * CC_BM;
+    const int rows = min(CC_BM, N - n0);
+    const int64_t mr0 = (int64_t)b * N + n0;
+    const int64_t slot = (int64_t)b * nch + ch;
+    for (int e = tid; e < CC_BM * 16; e += CC_T) {
+        const int r = e >> 4, q = (e & 15) * 4;
+        const float4 v = r < rows ? cc_ld4(x + (mr0 + r) * ldx + q) : make_float4(0.f, 0.f, 0.f, 0.f);
+        xs[r * CC_LDX + q] = v.x; xs[r * CC_LDX + q + 1] = v.y; xs[r * CC_LDX + q + 2] = v.z; xs[r * CC_LDX + q + 3] = v.w;
+    }
+    cc_floatx16 dxa[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dxa[j][r] = 0.f;
+    for (int o0 = 0; o0 < Cout; o0 += CC_OB) {
+        __syncthreads();                 // (the previous block's readers of gs / wt are done; the first time: xs is written)
+        for (int e = tid; e < CC_BM * (CC_OB / 4); e += CC_T) {
+            const int r = e >> 4, q = (e & 15) * 4, o = o0 + q;
+            float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (r < rows) {
+                const float4 zz = cc_ld4(dz + (mr0 + r) * Cout + o), yy = cc_ld4(yv + (mr0 + r) * Cout + o);
+                const float4 sc = cc_ld4(scale + o), sh = cc_ld4(shift + o), mu = cc_ld4(mean + o), is = cc_ld4(invstd + o);
+                const float4 k1 = cc_ld4(c1 + o), k2 = cc_ld4(c2 + o);
+                // dy = scale (p - c1 - xhat c2), p = dz where scale y + shift > 0 (mlp_loaders.h: dy_elem)
+                d.x = sc.x * ((((fmaf(sc.x, yy.x, sh.x) > 0.f) ? zz.x : 0.f) - k1.x) - (yy.x - mu.x) * is.x * k2.x);
+                d.y = sc.y * ((((fmaf(sc.y, yy.y, sh.y) > 0.f) ? zz.y : 0.f) - k1.y) - (yy.y - mu.y) * is.y * k2.y);
+                d.z = sc.z * ((((fmaf(sc.z, yy.z, sh.z) > 0.f) ? zz.z : 0.f) - k1.z) - (yy.z - mu.z) * is.z * k2.z);
+                d.w = sc.w * ((((fmaf(sc.w, yy.w, sh.w) > 0.f) ? zz.w : 0.f) - k1.w) - (yy.w - mu.w) * is.w * k2.w);
+            }
+            cc_st4(&gs[r * CC_LDA + q], d);
+        }
+        for (int e = tid; e < CC_OB * (CC_CP / 4); e += CC_T) {
+            const int o = e >> 4, k = (e & 15) * 4;
+            const float4 v = cc_ld4(w + (int64_t)(o0 + o) * ldw + k);
+            wt[k * CC_LDA + o] = v.x; wt[(k + 1) * CC_LDA + o] = v.y; wt[(k + 2) * CC_LDA + o] = v.z; wt[(k + 3) * CC_LDA + o] = v.w;
+        }
+        __syncthreads();
+        // dX[m][k] += sum_o dY[m][o] W[o][k]:  A[m][o] = gs, B[o][k] = wt[k][o]
+#pragma unroll
+        for (int oo = 0; oo < CC_OB; oo += 8) {
+            const float4 a = cc_ld4(&gs[(wv * 32 + l31) * CC_LDA + oo + 4 * hi]);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const float4 bq = cc_ld4(&wt[(j * 32 + l31) * CC_LDA + oo + 4 * hi]);
+                dxa[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, bq.x, dxa[j], 0, 0, 0);
+                dxa[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, bq.y, dxa[j], 0, 0, 0);
+                dxa[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, bq.z, dxa[j], 0, 0, 0);
+                dxa[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, bq.w, dxa[j], 0, 0, 0);
+            }
+        }
+        // partial dW_p[o][k] = sum_r dY[r][o] X[r][k]:  A[o][r] = gs[r][o], B[r][k] = xs[r][k]; wave: o block (wv & 1), k block (wv >> 1)
+        const int ob = (wv & 1) * 32, kb = (wv >> 1) * 32;
+        cc_floatx16 dwa;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dwa[r] = 0.f;
+#pragma unroll 8
+        for (int r0 = 0; r0 < CC_BM; r0 += 2)
+            dwa = __builtin_amdgcn_mfma_f32_32x32x2f32(gs[(r0 + hi) * CC_LDA + ob + l31], xs[(r0 + hi) * CC_LDX + kb + l31], dwa, 0, 0, 0);
+        float *pw = part_w + (slot * Cout + o0 + ob) * CC_CP + kb + l31;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) pw[(int64_t)((r & 3) + 8 * (r >> 2) + 4 * hi) * CC_CP] = dwa[r];
+        // partial column sums: lane = column 16 wv + (lane & 15), rows 32 (lane >> 4) .. + 31, then the four row quarters in fixed order
+        {
+            const int cl = wv * 16 + (lane & 15), rq = (lane >> 4) * 32;
+            float sacc = 0.f;
+#pragma unroll 8
+            for (int r = 0; r < 32; ++r) sacc += gs[(rq + r) * CC_LDA + cl];
+            sacc += __shfl_xor(sacc, 16);
+            sacc += __shfl_xor(sacc, 32);
+            if (lane < 16) part_s[slot * Cout + o0 + cl] = sacc;
+        }
+    }
+    if (dx) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int rr = wv * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                if (rr < rows) {
+                    float *p = dx + (mr0 + rr) * ldd + j * 32 + l31;
+                    *p = accumulate ? *p + dxa[j][r] : dxa[j][r];
+                }
+            }
+    }
+}
+
+// dW_p[o][k] (into w's layout, ldw) = sum over the T = B * nch chunks, in order; s[b][o] = sum over cloud b's nch chunks, in order
+__global__ __launch_bounds__(CC_T) void cc_fold_kernel(const float *__restrict__ part_w, const float *__restrict__ part_s, int B, int nch, int Cout,
+                                                       float *__restrict__ dw, int64_t ldw, float *__restrict__ s)
+{
+    const int64_t t = (int64_t)blockIdx.x * CC_T + threadIdx.x;
+    const int64_t nw = (int64_t)Cout * CC_CP;
+    if (t < nw) {
+        const int T = B * nch;
+        const float *p = part_w + t;
+        float a = 0.f;
+        int c = 0;
+        for (; c + 4 <= T; c += 4) {
+            const float v0 = p[(int64_t)c * nw], v1 = p[(int64_t)(c + 1) * nw], v2 = p[(int64_t)(c + 2) * nw], v3 = p[(int64_t)(c + 3) * nw];
+            a += v0; a += v1; a += v2; a += v3;
+        }
+        for (; c < T; ++c) a += p[(int64_t)c * nw];
+        dw[(t / CC_CP) * ldw + (t % CC_CP)] = a;
+        return;
+    }
+    const int64_t u = t - nw;
+    if (u >= (int64_t)B * Cout) return;
+    const int64_t b = u / Cout, o = u - b * Cout;
+    const float *p = part_s + b * nch * Cout + o;
+    float a = 0.f;
+    for (int c = 0; c < nch; ++c) a += p[(int64_t)c * Cout];
+    s[u] = a;
+}
+
+// from s [B, Cout]: dW_g[o][k] = sum_b s[b][o] g[b][k] (into w's layout at column Cp + k), dg[b][k] = sum_o s[b][o] W[o][Cp + k],
+// d bias[o] = sum_b s[b][o]
+__global__ __launch_bounds__(CC_T) void cc_tail_kernel(const float *__restrict__ s, const float *__restrict__ g, const float *__restrict__ w, int64_t ldw,
+                                                       int B, int Cp, int Cg, int Cout, float *__restrict__ dw, float *__restrict__ dbias,
+                                                       float *__restrict__ dg)
+{
+    const int64_t t = (int64_t)blockIdx.x * CC_T + threadIdx.x;
+    const int64_t n1 = (int64_t)Cout * Cg, n2 = n1 + (dg ? (int64_t)B * Cg : 0), n3 = n2 + (dbias ? Cout : 0);
+    if (t < n1) {
+        const int64_t o = t / Cg, k = t - o * Cg;
+        float a = 0.f;
+        for (int b = 0; b < B; ++b) a = fmaf(s[(int64_t)b * Cout + o], g[(int64_t)b * Cg + k], a);
+        dw[o * ldw + Cp + k] = a;
+    } else if (t < n2) {
+        const int64_t u = t - n1, b = u / Cg, k = u - b * Cg;
+        const float *sb = s + b * Cout;
+        const float *wk = w + Cp + k;
+        float a = 0.f;
+#pragma unroll 8
+        for (int o = 0; o < Cout; ++o) a = fmaf(sb[o], wk[(int64_t)o * ldw], a);
+        dg[u] = a;
+    } else if (t < n3) {
+        const int64_t o = t - n2;
+        float a = 0.f;
+        for (int b = 0; b < B; ++b) a += s[(int64_t)b * Cout + o];
+        dbias[o] = a;
+    }
+}
+
+static int cc_shape_ok(const char *who, int B, int N, int Cp, int Cg, int Cout)
+{
+    PAPC_REQUIRE(Cp == CC_CP && Cg >= 64 && Cg <= 1024 && Cg % 64 == 0 && Cout == 512, PAPC_E_UNSUPPORTED,
+                 "%s: Cp=%d Cg=%d Cout=%d (Cp = 64, Cg in 64..1024 and a multiple of 64, Cout = 512)", who, Cp, Cg, Cout);
+    PAPC_REQUIRE(B >= 1 && B <= 65535 && N >= 1 && (int64_t)B * N <= ((int64_t)1 << 30), PAPC_E_INVALID, "%s: B=%d N=%d", who, B, N);
+    return PAPC_OK;
+}
+
+static int64_t cc_chunks(int N) { return cdiv(N, CC_BM); }
+
+}  // namespace papc
+
+using namespace papc;
+
+extern "C" {
+
+int papc_cloud_concat_conv_parts(int B, int N)
+{
+    if (B < 1 || N < 1) return 0;
+    return (int)cdiv((int64_t)B * N, CC_BM);
+}
+
+int papc_cloud_concat_conv_f32(const float *x, int64_t ldx, const float *g, const float *w, const float *bias, int B, int N, int Cp, int Cg, int Cout,
+                               float *y, float *cvec, float *stats_partial, papc_stream_t stream)
+{
+    PAPC_REQUIRE(x && g && w && y && cvec, PAPC_E_INVALID, "papc_cloud_concat_conv_f32: null pointer");
+    const int err = cc_shape_ok("papc_cloud_concat_conv_f32", B, N, Cp, Cg, Cout);
+    if (err != PAPC_OK) return err;
+    PAPC_REQUIRE(ldx >= Cp && ldx % 4 == 0 && aligned16(x) && aligned16(w), PAPC_E_INVALID,
+                 "papc_cloud_concat_conv_f32: x and w must be 16-byte aligned, ldx=%lld a multiple of 4 >= Cp", (long long)ldx);
+    hipStream_t st = as_stream(stream);
+    ProfScope prof(PAPC_K_MISC, st);
+    const int64_t ldw = (int64_t)Cp + Cg;
+    const int M = B * N;
+    hipLaunchKernelGGL(cc_cvec_kernel, dim3((unsigned)(Cout / 16), (unsigned)B), dim3(CC_T), 0, st, g, w, ldw, bias, Cp, Cg, Cout, cvec);
+    const int e = check_launch("papc_cloud_concat_conv_f32: c");
+    if (e != PAPC_OK) return e;
+    hipLaunchKernelGGL(cc_fwd_kernel, dim3((unsigned)(Cout / CC_BN), (unsigned)cdiv(M, CC_BM)), dim3(CC_T), 0, st, x, ldx, w, ldw, cvec, M, N, Cout, y,
+                       stats_partial);
+    return check_launch("papc_cloud_concat_conv_f32");
+}
+
+size_t papc_cloud_concat_conv_bwd_workspace(int B, int N, int Cp, int Cg, int Cout)
+{
+    if (B < 1 || N < 1 || Cp != CC_CP || Cout != 512 || Cg < 64 || Cg > 1024 || Cg % 64) return 0;
+    const size_t T = (size_t)B * (size_t)cc_chunks(N);
+    return (T * (size_t)Cout * CC_CP + T * (size_t)Cout + (size_t)B * Cout) * sizeof(float);
+}
+
+int papc_cloud_concat_conv_bwd_f32(const float *dz, const float *y, const float *mean, const float *invstd, const float *scale, const float *shift,
+                                   const float *c1, const float *c2, const float *x, int64_t ldx, const float *g, const float *w, int B, int N, int Cp,
+                                   int Cg, int Cout, float *dx, int64_t ldd, int accumulate, float *dw, float *dbias, float *dg, float *s_out,
+                                   void *workspace, size_t workspace_bytes, papc_stream_t stream)
+{
+    PAPC_REQUIRE(dz && y && mean && invstd && scale && shift && c1 && c2 && x && g && w && dw && workspace, PAPC_E_INVALID,
+                 "papc_cloud_concat_conv_bwd_f32: null pointer");
+    const int err = cc_shape_ok("papc_cloud_concat_conv_bwd_f32", B, N, Cp, Cg, Cout);
+    if (err != PAPC_OK) return err;
+    PAPC_REQUIRE(ldx >= Cp && ldx % 4 == 0 && aligned16(x) && aligned16(w) && aligned16(dz) && aligned16(y) && aligned16(mean) && aligned16(invstd)
+                 && aligned16(scale) && aligned16(shift) && aligned16(c1) && aligned16(c2) && (!dx || ldd >= Cp), PAPC_E_INVALID,
+                 "papc_cloud_concat_conv_bwd_f32: operands must be 16-byte aligned, ldx=%lld a multiple of 4 >= Cp, ldd=%lld >= Cp",
+                 (long long)ldx, (long long)ldd);
+    const size_t need = papc_cloud_concat_conv_bwd_workspace(B, N, Cp, Cg, Cout);
+    PAPC_REQUIRE(workspace_bytes >= need, PAPC_E_INVALID, "papc_cloud_concat_conv_bwd_f32: workspace %zu bytes < %zu", workspace_bytes, need);
+    hipStream_t st = as_stream(stream);
+    ProfScope prof(PAPC_K_MISC, st);
+    const int64_t ldw = (int64_t)Cp + Cg;
+    const int nch = (int)cc_chunks(N);
+    const int64_t T = (int64_t)B * nch;
+    float *part_w = static_cast<float *>(workspace);
+    float *part_s = part_w + T * Cout * CC_CP;
+    float *s = s_out ? s_out : part_s + T * Cout;
+    hipLaunchKernelGGL(cc_bwd_kernel, dim3((unsigned)nch, (unsigned)B), dim3(CC_T), 0, st, dz, y, mean, invstd, scale, shift, c1, c2, x, ldx, w, ldw, N,
+                       Cout, dx, ldd, accumulate, part_w, part_s);
+    int e = check_launch("papc_cloud_concat_conv_bwd_f32");
+    if (e != PAPC_OK) return e;
+    const int64_t n_fold = (int64_t)Cout * CC_CP + (int64_t)B * Cout;
+    hipLaunchKernelGGL(cc_fold_kernel, dim3((unsigned)cdiv(n_fold, CC_T)), dim3(CC_T), 0, st, part_w, part_s, B, nch, Cout, dw, ldw, s);
+    e = check_launch("papc_cloud_concat_conv_bwd_f32: fold");
+    if (e != PAPC_OK) return e;
+    const int64_t n_tail = (int64_t)Cout * Cg + (dg ? (int64_t)B * Cg : 0) + (dbias ? Cout : 0);
+    hipLaunchKernelGGL(cc_tail_kernel, dim3((unsigned)cdiv(n_tail, CC_T)), dim3(CC_T), 0, st, s, g, w, ldw, B, Cp, Cg, Cout, dw, dbias, dg);
+    return check_launch("papc_cloud_concat_conv_bwd_f32: tail");
+}
+
+}  // extern "C"

@@ -4,6 +4,8 @@
   PointNet_Basic_Clas                      <- /root/reference/PAPC/models/classify/pointnet_base/pointnet_base.py:4-47
   PointNet_Clas (T-Net PointNet)           <- /root/reference/PAPC/models/classify/pointnet/pointnet_Conv1D.py:4-104
   PointNet2_SSG_Seg / PointNet2_MSG_Seg    <- /root/reference/PAPC/models/segment/pointnet2/pointnet2.py:6-52, :54-100
+  PointNet_Seg (T-Net PointNet)            <- /root/reference/PAPC/models/segment/pointnet/pointnet.py:4-114
+  PointNet_Basic_Seg                       <- /root/reference/PAPC/models/segment/pointnet_base/pointnet_base.py:4-80
 
 Inputs are ``[B,3,N]`` float32 (``[B,6,N]`` with normals).  Everything runs in libpapc_hip.so, in train AND eval mode, the FC heads included
 (head.py); the nn.Linear / BatchNorm1d / Dropout modules are the parameter holders.  CPU tensors raise PapcError (there is no CPU path); the
@@ -293,6 +295,117 @@ class PointNet_Clas(nn.Module):
         if _FUSED_HEAD and _head.plain_usable(feat, self.fc[0], self.fc[2], self.fc[5], self.training):
             return _head.plain_head(self._spec("_head_spec"), feat, self.fc[0], self.fc[2], self.fc[4], self.fc[5], training=self.training)   # :102
         return self.fc(feat)                                                                           # :102
+
+
+def _seg_net(cin, num_classes):
+    """seg_net of both PointNet segmenters (segment/pointnet/pointnet.py:68-82, pointnet_base/pointnet_base.py:9-23): [Conv1D, BN, ReLU] x 4
+    (cin -> 512 -> 256 -> 128 -> 128) and Conv1D(128, num_classes), at the source's indices 0..12"""
+    return nn.Sequential(*(list(_conv_bn_relu([cin, 512, 256, 128, 128])) + [nn.Conv1d(128, num_classes, 1)]))
+
+
+def _seg_input(model, inputs):
+    """inputs[0] as the source takes it (the seg loader's [data, label] batch), or a bare [B, 3, N] tensor; a numpy array goes to the model's
+    device (paddle.to_tensor), a CPU tensor raises PapcError"""
+    import numpy as np
+    if isinstance(inputs, (list, tuple)):
+        inputs = inputs[0]
+    if isinstance(inputs, np.ndarray):
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise _lib.PapcError("%s needs its parameters on a CUDA (ROCm) device: there is no CPU fallback" % type(model).__name__)
+        inputs = torch.from_numpy(np.ascontiguousarray(inputs, dtype=np.float32)).to(dev)
+    x = torch.as_tensor(inputs).float()
+    if not x.is_cuda:
+        raise _lib.PapcError("%s needs CUDA (ROCm) tensors: there is no CPU fallback" % type(model).__name__)
+    return x
+
+
+def _seg_head(model, point_rows, global_feat, B, N):
+    """concat + seg_net (pointnet.py:105-114): seg_net[0..2] on segment.cloud_concat_bn_relu (the tile is never formed), [3..11] on one
+    shared-MLP stack without the max, [12] on linear.linear_rows -> logits [B, N, num_classes]"""
+    from .linear import linear_rows
+    from .segment import cloud_concat_bn_relu
+    s = model.seg_net
+    h = cloud_concat_bn_relu(point_rows, global_feat, s[0], s[1], N, model.training)    # [B*N, 512]
+    h = model._stack(list(s)[3:12], B, N, False, x_rows=h)                              # [B*N, 128]
+    return linear_rows(h, s[12].weight, s[12].bias).view(B, N, -1)
+
+
+class PointNet_Seg(nn.Module):
+    """PointNet part segmentation with an input and a feature T-Net (/root/reference/PAPC/models/segment/pointnet/pointnet.py:4-114).
+
+    The T-Nets, mlp_1 and the feature transform run as in PointNet_Clas; mlp_2 pools on the stack (the global feature); seg_net as _seg_head.
+    Containers and indices are the source's, so checkpoint.export_state / import_state exchange .pdparams with it directly.  The source tiles
+    the global feature by max_point: inputs must have N == max_point.  Output [B, N, num_classes]."""
+
+    _spec = PointNet_Clas._spec
+    _stack = PointNet_Clas._stack
+
+    def __init__(self, num_classes=50, max_point=2048):
+        super().__init__()
+        self.max_point = int(max_point)
+        self.input_transform_net = _conv_bn_relu([3, 64, 128, 1024], pool=max_point)                      # :8-20
+        self.input_fc = nn.Sequential(nn.Linear(1024, 512), nn.ReLU(), nn.Linear(512, 256), nn.ReLU(), nn.Linear(256, 9))   # :21-30
+        with torch.no_grad():
+            self.input_fc[4].weight.zero_()                                                                  # :27 Assign(zeros)
+            self.input_fc[4].bias.copy_(torch.eye(3).reshape(-1))                                            # :28 Assign(eye(3))
+        self.mlp_1 = _conv_bn_relu([3, 64, 64])                                                              # :31-38
+        self.feature_transform_net = _conv_bn_relu([64, 64, 128, 1024], pool=max_point)                     # :39-51
+        self.feature_fc = nn.Sequential(nn.Linear(1024, 512), nn.ReLU(), nn.Linear(512, 256), nn.ReLU(), nn.Linear(256, 64 * 64))  # :52-58
+        self.mlp_2 = _conv_bn_relu([64, 64, 128, 1024])                                                      # :59-68
+        self.seg_net = _seg_net(1024 + 64, num_classes)                                                      # :69-83
+
+    def forward(self, inputs):
+        x = _seg_input(self, inputs)                                          # :85 inputs[0], [B,3,N]
+        B, _, N = x.shape
+        if N != self.max_point:
+            raise _lib.PapcError("PointNet_Seg: the source tiles the global feature by max_point: N = %d points per cloud, max_point = %d" % (N, self.max_point))
+        from .transform import tnet_fc, transform_points, transform_rows
+        g = self._stack(self.input_transform_net, B, N, True, xyz=x.transpose(1, 2), zero=_lib.const_zeros((B, 1, 3), x.device))   # :88-89
+        t_in = tnet_fc(self._spec("_spec_input_fc"), g, self.input_fc).view(B, 3, 3)                   # :90-91
+        pts = transform_points(x, t_in)                                                                # :93-95 -> [B, N, 3]
+        h = self._stack(self.mlp_1, B, N, False, x_rows=pts.view(B * N, 3))                            # :96 -> [B*N, 64]
+        g = self._stack(self.feature_transform_net, B, N, True, x_rows=h)                              # :98-99
+        t_feat = tnet_fc(self._spec("_spec_feature_fc"), g, self.feature_fc).view(B, 64, 64)           # :100-101
+        point_feat = transform_rows(h, t_feat, N)                                                      # :103-107
+        g = self._stack(self.mlp_2, B, N, True, x_rows=point_feat)                                     # :108-109 -> [B, 1024]
+        return _seg_head(self, point_feat, g, B, N)                                                    # :110-114
+
+
+class _PointNetBasicFeatures(nn.Module):
+    """The source's PointNet_Basic of the segmenter (segment/pointnet_base/pointnet_base.py:41-76): the holders of mlp_1 / mlp_2"""
+
+    def __init__(self, max_points=1024):
+        super().__init__()
+        self.mlp_1 = _conv_bn_relu([3, 64, 64])                          # :44-51
+        self.mlp_2 = _conv_bn_relu([64, 64, 128, max_points])            # :52-62
+
+
+class PointNet_Basic_Seg(nn.Module):
+    """PointNet-Basic part segmentation (/root/reference/PAPC/models/segment/pointnet_base/pointnet_base.py:4-80): mlp_1 (per point) and
+    mlp_2 pooled over each cloud (max_points channels) on the shared-MLP stack, then seg_net as PointNet_Seg's.  ``pointnet_bacic`` is the
+    source's spelling, kept so that .pdparams load with no name table.  Inputs must have N == max_points.  Output [B, N, num_classes]."""
+
+    _spec = PointNet_Clas._spec
+    _stack = PointNet_Clas._stack
+
+    def __init__(self, num_classes=50, max_points=1024):
+        super().__init__()
+        self.max_points = int(max_points)
+        self.pointnet_bacic = _PointNetBasicFeatures(max_points)         # :7
+        self.seg_net = _seg_net(max_points + 64, num_classes)            # :8-22
+
+    def forward(self, inputs):
+        x = _seg_input(self, inputs)                                     # :30 inputs[0], [B,3,N]
+        B, _, N = x.shape
+        if N != self.max_points:
+            raise _lib.PapcError("PointNet_Basic_Seg: the source tiles the global feature by max_points: N = %d points per cloud, max_points = %d"
+                                 % (N, self.max_points))
+        from .copyops import contiguous_copy
+        pts = contiguous_copy(x.transpose(1, 2)).view(B * N, 3)          # the planar coordinates as point rows
+        h = self._stack(self.pointnet_bacic.mlp_1, B, N, False, x_rows=pts)   # :31 x1 -> [B*N, 64]
+        g = self._stack(self.pointnet_bacic.mlp_2, B, N, True, x_rows=h)      # :31-32 max(x2) -> [B, max_points]
+        return _seg_head(self, h, g, B, N)                               # :33-39
 
 
 def Categorical(y, num_class=16):
