@@ -176,6 +176,7 @@ SIGNATURES = {
     "papc_pg_prep_weights_f32": (c_i, [c_p, c_i, c_p]),
     "papc_pg_prep_rows_f32": (c_i, [c_p, c_p]),
     "papc_pg_gemm_f32": (c_i, [c_p, c_p]),
+    "papc_pg_gemm_group_f32": (c_i, [c_p, c_i, c_p]),
     "papc_pg_final_f32": (c_i, [c_p, c_i, c_l, c_i, c_p, c_p, c_f, c_f] + [c_p] * 10 + [c_l, c_p, c_p, c_p]),
     "papc_pg_final_groups_f32": (c_i, [c_p, c_i, c_l, c_i, c_p, c_p, c_f, c_f] + [c_p] * 10 + [c_l, c_i, c_p, c_p, c_p, c_p]),
     "papc_pg_fold_f32": (c_i, [c_p, c_i, c_p]),

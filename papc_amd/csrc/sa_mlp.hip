@@ -401,33 +401,31 @@ static int planes_bwd(const papc_sa_plan &p, const papc_sa_io &io, const papc_sa
             a.mode = PAPC_PG_DY_DENSE; a.dz = dz; a.red = red; a.red_parts = (int)T;
         }
         SA_CALL(papc_pg_prep_rows_f32(&a, st));
-        // ---- dX
+        // ---- dX and dW = dY^T . input (contraction over the M rows, split over workgroups, partials folded at the end): independent
+        // products of the dY planes just written, in one launch
+        papc_pg_gemm g[2];
+        memset(g, 0, sizeof(g));
+        int ng = 0;
         float *dz_prev = nullptr, *red_prev = nullptr;
         if (l > 0) {
             const float *pc = s.cst[l - 1];
             dz_prev = b.dz[flip]; red_prev = b.red[flip];
             flip ^= 1;
-            papc_pg_gemm g;
-            memset(&g, 0, sizeof(g));
-            g.epi = PAPC_PG_RED; g.a = b.dyp; g.b = s.wtp[l]; g.R1 = (int)M; g.R2 = cin; g.K = cout;
-            g.c = dz_prev; g.ldc = cin; g.split = 1; g.stats = red_prev; g.family = PAPC_K_BWD_DX;
-            g.y_prev = s.y[l - 1]; g.mean = pc; g.invstd = pc + cin; g.scale = pc + 2 * cin; g.shift = pc + 3 * cin;
-            SA_CALL(papc_pg_gemm_f32(&g, st));
+            papc_pg_gemm &x = g[ng++];
+            x.epi = PAPC_PG_RED; x.a = b.dyp; x.b = s.wtp[l]; x.R1 = (int)M; x.R2 = cin; x.K = cout;
+            x.c = dz_prev; x.ldc = cin; x.split = 1; x.stats = red_prev; x.family = PAPC_K_BWD_DX;
+            x.y_prev = s.y[l - 1]; x.mean = pc; x.invstd = pc + cin; x.scale = pc + 2 * cin; x.shift = pc + 3 * cin;
         } else if (grad_in) {
             const int n_in = pg_n_in(p);
-            papc_pg_gemm g;
-            memset(&g, 0, sizeof(g));
-            g.epi = PAPC_PG_STORE; g.a = b.dyp; g.b = s.wtp[0]; g.R1 = (int)M; g.R2 = n_in; g.K = cout;
-            g.c = grad_in; g.ldc = n_in; g.split = 1; g.family = PAPC_K_BWD_DX;
-            SA_CALL(papc_pg_gemm_f32(&g, st));
+            papc_pg_gemm &x = g[ng++];
+            x.epi = PAPC_PG_STORE; x.a = b.dyp; x.b = s.wtp[0]; x.R1 = (int)M; x.R2 = n_in; x.K = cout;
+            x.c = grad_in; x.ldc = n_in; x.split = 1; x.family = PAPC_K_BWD_DX;
         }
-        // ---- dW = dY^T . input: contraction over the M rows, split over workgroups, partials folded at the end
         const int split = pg_split_for(cout, cin, (int)(M / 32));
-        papc_pg_gemm g;
-        memset(&g, 0, sizeof(g));
-        g.epi = PAPC_PG_STORE; g.a = b.dypt; g.b = s.PT[l]; g.R1 = cout; g.R2 = cin; g.K = (int)M;
-        g.c = b.part[l]; g.ldc = cin; g.split = split; g.split_stride = (int64_t)cout * cin; g.family = PAPC_K_BWD_DW;
-        SA_CALL(papc_pg_gemm_f32(&g, st));
+        papc_pg_gemm &w = g[ng++];
+        w.epi = PAPC_PG_STORE; w.a = b.dypt; w.b = s.PT[l]; w.R1 = cout; w.R2 = cin; w.K = (int)M;
+        w.c = b.part[l]; w.ldc = cin; w.split = split; w.split_stride = (int64_t)cout * cin; w.family = PAPC_K_BWD_DW;
+        SA_CALL(papc_pg_gemm_group_f32(g, ng, st));
         if (!defer_fold(gr, b.part[l], split, (int64_t)cout * cin, 1, cout * cin, gr.dw[l], (int64_t)cout * cin, acc_w ? 1 : 0))
             fold[n_fold++] = papc_pg_fold_job{b.part[l], split, (int64_t)cout * cin, (int64_t)cout * cin, gr.dw[l], acc_w ? 1 : 0};
         if (gr.db[l] && !acc_w) SA_CALL(papc_fill_f32(gr.db[l], cout, 0.f, st));      // (a bias feeding a train-mode BN: gradient exactly 0)

@@ -386,23 +386,23 @@ __device__ __forceinline__ void pg_epilogue(const PgArgs &p, floatx16 (&acc)[2][
     }
 }
 
-// NS = stages in the LDS ring (NS - 1 of them in flight): 3 stages x 48 KiB is one workgroup per CU; (NB = 1, NS = 2) is 72 KiB, two
-// workgroups per CU whose waves fill each other's LDS-read and barrier gaps.
+template <int NB>
+constexpr int pg_stage_bytes() { return (4 + 2 * NB) * 6 * 1024; }   // 32-row blocks of a stage (4 of A, then 2 NB of B) x 6 KiB: [2 k16][3 planes][1 KiB]
+
+// One workgroup of a product: workgroup t of the product's nwg, on the LDS ring smem (NS stages of pg_stage_bytes<NB>()).
 template <int EPI, int NB, int NS>
-__global__ __launch_bounds__(256, 1) void pg_gemm_kernel(PgArgs p)
+__device__ __forceinline__ void pg_gemm_wg(const PgArgs &p, int t, const int nwg, char *smem)
 {
-    constexpr int NRB = 4 + 2 * NB;              // 32-row blocks per stage: 4 of A, then 2 NB of B
-    constexpr int STAGE = NRB * 6 * 1024;        // a (row block, k32) piece is 6 KiB: [2 k16][3 planes][1 KiB]
-    constexpr int NLW = NRB * 6 / 4;             // fragment loads per wave and stage
-    __shared__ __attribute__((aligned(1024))) char smem[NS * STAGE];
+    constexpr int STAGE = pg_stage_bytes<NB>();
+    constexpr int NLW = (4 + 2 * NB) * 6 / 4;    // fragment loads per wave and stage
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int wr = w >> 1, wc = w & 1;
     // workgroup -> (split z, row tile bi, column tile bj).  Consecutive workgroup ids go round-robin to the 8 XCDs (one L2 each): give
     // every XCD a CONTIGUOUS range of the (z, bi, bj) order, so that it streams one k range of few row tiles against all column tiles
     // (forward / dX) or all tiles of one k range (dW) through its own L2 instead of every XCD pulling every operand from the fabric.
-    int t = blockIdx.x;
-    const int nwg = gridDim.x;
+    // (In a grouped launch t is relative to the product's first workgroup, which starts on XCD 0 when the products before it have
+    // whole multiples of 8 workgroups.)
     if ((nwg & 7) == 0) t = (t & 7) * (nwg >> 3) + (t >> 3);
     const int tiles = p.g1 * p.g2;
     const int bz = t / tiles;
@@ -493,6 +493,28 @@ __global__ __launch_bounds__(256, 1) void pg_gemm_kernel(PgArgs p)
     const bool full = bi * 128 + 128 <= p.R1 && (bj + 1) * (NB * 64) <= p.R2;
     if (full) pg_epilogue<EPI, NB, true>(p, acc, smem, lane, wr, wc, bi, bj, bz);
     else pg_epilogue<EPI, NB, false>(p, acc, smem, lane, wr, wc, bi, bj, bz);
+}
+
+// NS = stages in the LDS ring (NS - 1 of them in flight): 3 stages x 48 KiB is one workgroup per CU; (NB = 1, NS = 2) is 72 KiB, two
+// workgroups per CU whose waves fill each other's LDS-read and barrier gaps.
+template <int EPI, int NB, int NS>
+__global__ __launch_bounds__(256, 1) void pg_gemm_kernel(PgArgs p)
+{
+    __shared__ __attribute__((aligned(1024))) char smem[NS * pg_stage_bytes<NB>()];
+    pg_gemm_wg<EPI, NB, NS>(p, blockIdx.x, gridDim.x, smem);
+}
+
+// Two independent products in one grid (a layer's dX and its split-K dW): workgroups [0, n0) run product 0, the rest product 1, each
+// with its own tile numbering and epilogue and the arithmetic of its own launch.  One (NB = 1, NS = 2) ring of 72 KiB for both, so
+// two workgroups share a CU whichever products they belong to, and the second product's workgroups fill the CUs the first leaves
+// idle -- without the graph edge a parallel branch costs.
+template <int EPI0, int EPI1>
+__global__ __launch_bounds__(256, 1) void pg_gemm_group_kernel(PgArgs p0, PgArgs p1, int n0)
+{
+    __shared__ __attribute__((aligned(1024))) char smem[2 * pg_stage_bytes<1>()];
+    const int t = blockIdx.x;
+    if (t < n0) pg_gemm_wg<EPI0, 1, 2>(p0, t, n0, smem);
+    else pg_gemm_wg<EPI1, 1, 2>(p1, t - n0, (int)gridDim.x - n0, smem);
 }
 
 // ---- last forward layer: batch statistics -> BN constants, then BN + ReLU on the selected extreme of every (group, channel) ------
@@ -687,7 +709,12 @@ int papc_pg_prep_rows_f32(const papc_pg_prep *a, papc_stream_t stream)
     return check_launch("papc_pg_prep_rows_f32");
 }
 
-int papc_pg_gemm_f32(const papc_pg_gemm *g, papc_stream_t stream)
+}  // extern "C"
+
+namespace papc {
+
+// papc_pg_gemm -> kernel arguments (validated); *split = the product's split-K factor
+static int pg_args(const papc_pg_gemm *g, PgArgs &p, int *split_out)
 {
     PAPC_REQUIRE(g && g->a && g->b && g->c, PAPC_E_INVALID, "papc_pg_gemm_f32: null pointer");
     PAPC_REQUIRE(g->R1 >= 1 && g->R2 >= 1 && g->K >= 1 && g->ldc >= g->R2, PAPC_E_INVALID, "papc_pg_gemm_f32: bad sizes");
@@ -696,12 +723,12 @@ int papc_pg_gemm_f32(const papc_pg_gemm *g, papc_stream_t stream)
     const int split = g->split >= 1 ? g->split : 1;
     PAPC_REQUIRE(nst_all % split == 0, PAPC_E_INVALID, "papc_pg_gemm_f32: split %d does not divide the %d k32 stages", split, nst_all);
     PAPC_REQUIRE(split == 1 || g->epi == PG_EPI_STORE, PAPC_E_INVALID, "papc_pg_gemm_f32: split K only with the plain store epilogue");
-    PgArgs p;
     memset(&p, 0, sizeof(p));
     p.a = reinterpret_cast<const char *>(g->a); p.b = reinterpret_cast<const char *>(g->b); p.KB = nst_all * 2; p.nst = nst_all / split;
     p.R1 = g->R1; p.R2 = g->R2; p.c = g->c; p.ldc = g->ldc; p.zstride = g->split_stride;
     p.bias = g->bias; p.stats = g->stats; p.dbg = knob(KNOB_PG_DBG);
     const int epi = g->epi;
+    PAPC_REQUIRE(epi >= PG_EPI_STORE && epi <= PG_EPI_RED, PAPC_E_INVALID, "papc_pg_gemm_f32: bad epilogue %d", epi);
     if (epi == PG_EPI_FWD || epi == PG_EPI_FWD_GMAX || epi == PG_EPI_RED) PAPC_REQUIRE(g->stats, PAPC_E_INVALID, "papc_pg_gemm_f32: this epilogue needs stats");
     if (epi == PG_EPI_FWD_GMAX) {
         PAPC_REQUIRE(g->gmax && g->gmin && g->amax && g->amin && g->R1 % 128 == 0, PAPC_E_INVALID, "papc_pg_gemm_f32: GMAX needs its four arrays and whole 128-row groups");
@@ -711,6 +738,21 @@ int papc_pg_gemm_f32(const papc_pg_gemm *g, papc_stream_t stream)
         PAPC_REQUIRE(g->y_prev && g->mean && g->invstd && g->scale && g->shift && g->ldc == g->R2, PAPC_E_INVALID, "papc_pg_gemm_f32: RED needs the layer below (dense)");
         p.y_prev = g->y_prev; p.mean = g->mean; p.invstd = g->invstd; p.scale = g->scale; p.shift = g->shift;
     }
+    *split_out = split;
+    return PAPC_OK;
+}
+
+}  // namespace papc
+
+extern "C" {
+
+int papc_pg_gemm_f32(const papc_pg_gemm *g, papc_stream_t stream)
+{
+    PgArgs p;
+    int split = 1;
+    const int rc = pg_args(g, p, &split);
+    if (rc != PAPC_OK) return rc;
+    const int epi = g->epi;
     hipStream_t st = as_stream(stream);
     ProfScope prof(g->family >= 0 && g->family < PAPC_K_COUNT ? g->family : PAPC_K_MISC, st);
     // Tile flavours.  (NB = 2, NS = 3): 128 x 128 tiles, 144 KiB of LDS, one workgroup (one wave per SIMD) per CU -- the least operand
@@ -734,11 +776,48 @@ int papc_pg_gemm_f32(const papc_pg_gemm *g, papc_stream_t stream)
     case PG_EPI_STORE: PG_GO(PG_EPI_STORE); break;
     case PG_EPI_FWD: PG_GO(PG_EPI_FWD); break;
     case PG_EPI_FWD_GMAX: PG_GO(PG_EPI_FWD_GMAX); break;
-    case PG_EPI_RED: PG_GO(PG_EPI_RED); break;
-    default: set_error("papc_pg_gemm_f32: bad epilogue %d", epi); return PAPC_E_INVALID;
+    default: PG_GO(PG_EPI_RED); break;
     }
 #undef PG_GO
     return check_launch("papc_pg_gemm_f32");
+}
+
+int papc_pg_gemm_group_f32(const papc_pg_gemm *g, int count, papc_stream_t stream)
+{
+    PAPC_REQUIRE(g && (count == 1 || count == 2), PAPC_E_INVALID, "papc_pg_gemm_group_f32: 1 or 2 products");
+    PgArgs p[2];
+    int split[2] = {1, 1};
+    for (int i = 0; i < count; ++i) {
+        const int rc = pg_args(&g[i], p[i], &split[i]);
+        if (rc != PAPC_OK) return rc;
+        PAPC_REQUIRE(g[i].epi == PG_EPI_STORE || g[i].epi == PG_EPI_RED, PAPC_E_UNSUPPORTED,
+                     "papc_pg_gemm_group_f32: product %d: only the store and dX (RED) epilogues share a launch", i);
+    }
+    PAPC_REQUIRE(count == 1 || g[0].epi != PG_EPI_RED || g[1].epi != PG_EPI_RED, PAPC_E_UNSUPPORTED, "papc_pg_gemm_group_f32: at most one dX (RED) product per launch");
+    // PAPC_PG_GROUP=0, a lone product, or a tile flavour forced by PAPC_PG_NB / PAPC_PG_NS: one launch per product, in the given order
+    if (count == 1 || !knob(KNOB_PG_GROUP) || knob(KNOB_PG_NB) == 2 || knob(KNOB_PG_NS) == 3) {
+        for (int i = 0; i < count; ++i) {
+            const int rc = papc_pg_gemm_f32(&g[i], stream);
+            if (rc != PAPC_OK) return rc;
+        }
+        return PAPC_OK;
+    }
+    // one grid, both products on (NB = 1, NS = 2) tiles (the tile width does not change any element's accumulation order); the product
+    // with more k32 stages per workgroup first, so its workgroups start first and the shorter ones fill in behind them
+    int n[2];
+    for (int i = 0; i < 2; ++i) {
+        p[i].g1 = (int)cdiv(g[i].R1, 128); p[i].g2 = (int)cdiv(g[i].R2, 64);
+        n[i] = p[i].g1 * p[i].g2 * split[i];
+    }
+    const int f = p[1].nst > p[0].nst ? 1 : 0, s = 1 - f;
+    const int e0 = g[f].epi, e1 = g[s].epi;
+    hipStream_t st = as_stream(stream);
+    ProfScope prof(g[f].family >= 0 && g[f].family < PAPC_K_COUNT ? g[f].family : PAPC_K_MISC, st);
+    const dim3 grid((unsigned)(n[0] + n[1]));
+    if (e0 == PG_EPI_RED) hipLaunchKernelGGL((pg_gemm_group_kernel<PG_EPI_RED, PG_EPI_STORE>), grid, dim3(256), 0, st, p[f], p[s], n[f]);
+    else if (e1 == PG_EPI_RED) hipLaunchKernelGGL((pg_gemm_group_kernel<PG_EPI_STORE, PG_EPI_RED>), grid, dim3(256), 0, st, p[f], p[s], n[f]);
+    else hipLaunchKernelGGL((pg_gemm_group_kernel<PG_EPI_STORE, PG_EPI_STORE>), grid, dim3(256), 0, st, p[f], p[s], n[f]);
+    return check_launch("papc_pg_gemm_group_f32");
 }
 
 int papc_pg_final_f32(const float *stats, int parts, int64_t M, int C, const float *gamma, const float *beta, float eps, float momentum,

@@ -8,7 +8,8 @@ Same contract as mlp.SharedMLPMax (one autograd node per stack, only the pre-BN 
 built for M = B*128 rows where the row-GEMM kernels are latency-bound: every operand is written ONCE as fragment-ordered bf16
 planes by a prep kernel that also folds the train-mode BatchNorm statistics (forward) or the two BN-backward constants (backward)
 from the producer's per-tile partials, and every product of the stack -- forward, dX, dW -- is the same plane-set GEMM
-(include/papc_hip.h: papc_pg_*).  Launches per step: 8 forward, 10 backward (the row kernels needed 7 + 13).
+(include/papc_hip.h: papc_pg_*).  Launches per step: 8 forward, 7 backward (the row kernels needed 7 + 13): a layer's dX and dW
+share one launch (papc_pg_gemm_group_f32).
 """
 import ctypes
 import os
@@ -267,31 +268,34 @@ class PlanesMLPMax(torch.autograd.Function):
                 prep(mode=DY_MAX, gout=gout.data_ptr(), ysel=ysel.data_ptr(), argmax=argmax.data_ptr(), K=GROUP, **common)
             else:
                 prep(mode=DY_DENSE, dz=dz.data_ptr(), red=red.data_ptr(), red_parts=T, **common)
-            # ---- dX
+            # ---- dX and dW = dY^T . input (contraction over the M rows, split over workgroups, partials folded at the end): independent
+            # products of the dY planes just written, in one launch
+            gs = (PgGemm * 2)()
+            ng = 0
             if l > 0:
                 pc = consts[l - 1]
                 dz_prev = torch.empty(M, cin, device=dev, dtype=torch.float32)
                 red_prev = torch.empty(T, 2, cin, device=dev, dtype=torch.float32)
-                g = PgGemm()
+                g = gs[ng]
+                ng += 1
                 g.epi, g.a, g.b, g.R1, g.R2, g.K = EPI_RED, dyp.data_ptr(), wtp[l].data_ptr(), M, cin, cout
                 g.c, g.ldc, g.split, g.split_stride, g.stats, g.family = dz_prev.data_ptr(), cin, 1, 0, red_prev.data_ptr(), K_BWD_DX
                 g.y_prev, g.mean, g.invstd, g.scale, g.shift = ys[l - 1].data_ptr(), pc[0].data_ptr(), pc[1].data_ptr(), pc[2].data_ptr(), pc[3].data_ptr()
-                check(lib.papc_pg_gemm_f32(ctypes.byref(g), st), "papc_pg_gemm_f32")
             elif ctx.in_grad:
                 n_in = ctx.n_in
                 grad_in = torch.empty(M, n_in, device=dev, dtype=torch.float32)
-                g = PgGemm()
+                g = gs[ng]
+                ng += 1
                 g.epi, g.a, g.b, g.R1, g.R2, g.K = EPI_STORE, dyp.data_ptr(), wtp[0].data_ptr(), M, n_in, cout
                 g.c, g.ldc, g.split, g.split_stride, g.family = grad_in.data_ptr(), n_in, 1, 0, K_BWD_DX
-                check(lib.papc_pg_gemm_f32(ctypes.byref(g), st), "papc_pg_gemm_f32")
-            # ---- dW = dY^T . input: contraction over the M rows, split over workgroups, partials folded at the end
             split = _split_for(cout, cin, nst)
             part = torch.empty(split, cout * cin, device=dev, dtype=torch.float32)
             keep.append(part)
-            g = PgGemm()
+            g = gs[ng]
+            ng += 1
             g.epi, g.a, g.b, g.R1, g.R2, g.K = EPI_STORE, dypt.data_ptr(), PT[l].data_ptr(), cout, cin, M
             g.c, g.ldc, g.split, g.split_stride, g.family = part.data_ptr(), cin, split, cout * cin, K_BWD_DW
-            check(lib.papc_pg_gemm_f32(ctypes.byref(g), st), "papc_pg_gemm_f32")
+            check(lib.papc_pg_gemm_group_f32(gs, ng, st), "papc_pg_gemm_group_f32")
             if inplace:
                 fold.append((part.data_ptr(), split, cout * cin, cout * cin, tgt[0].data_ptr(), 1))
             else:
