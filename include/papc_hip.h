@@ -343,7 +343,7 @@ int papc_mlp_bwd_dw_f32(const papc_bwd_dy *dy, int a_mode, const float *x, int64
  * layers with a 64-channel BN+ReLU input wants exactly one residency wave of workgroups.  K: rows per group (PAPC_DZ_MAX), else 0. */
 int papc_mlp_bwd_dw_chunk_hint(int64_t M, int Cin, int Cout, int a_mode, int dz_mode, int K);
 
-/* out[i] (+)= sum_t partial[t, i]  (fixed order -> deterministic); n = elements per chunk; accumulate != 0 adds
+/* out[i] (+)= sum_t partial[t, i]  (fixed order, csrc/fold.h -> deterministic); n = elements per chunk; accumulate != 0 adds
  * into out (gradient accumulation straight into a parameter's .grad) */
 int papc_reduce_partials_f32(const float *partial, int n_chunks, int64_t n, float *out, int accumulate,
                              papc_stream_t stream);
@@ -364,7 +364,7 @@ int papc_reduce_partials2_f32(const float *partial, int n_chunks, int64_t ld, in
 
 /* Deferred folds: up to PAPC_FOLD_MAX partial reductions of ANY of the kinds above (a stack's dW / db partials, the strided xyz / feature
  * column blocks of the gather-add first layer, the split-K partials of the planes path) in ONE launch:
- *     out[r * out_ld + c] (+)= sum_{t < n_chunks} partial[t * ld + r * cols + c]      r < rows, c < cols      (fixed order)
+ *     out[r * out_ld + c] (+)= sum_{t < n_chunks} partial[t * ld + r * cols + c]      r < rows, c < cols      (fixed order: csrc/fold.h)
  * A training step folds the partials of ALL its stacks once, behind the last backward kernel, instead of 5-6 launch-latency-sized
  * kernels spread over the backward: papc_sa_mlp_bwd appends its jobs to papc_sa_grads.defer (a HOST list owned by the caller, who keeps
  * the backward scratch buffers alive until papc_fold_jobs_f32 has been enqueued) instead of launching them.  `jobs` is a HOST array. */
@@ -955,7 +955,7 @@ int papc_pg_final_groups_f32(const float *stats, int parts, int64_t M, int C, co
                              const float *gmin, const int32_t *amax, const int32_t *amin, int64_t G, int tiles_per_group, float *out, int32_t *argmax,
                              float *ysel, papc_stream_t stream);
 
-/* count <= 8 split-K partial sets folded in one launch, fixed order: out[e] (+)= sum_t partial[t*stride + e], e < n.  HOST array. */
+/* count <= 8 split-K partial sets folded in one launch, fixed order (csrc/fold.h): out[e] (+)= sum_t partial[t*stride + e], e < n.  HOST array. */
 typedef struct papc_pg_fold_job {
     const float *partial; int nsplit; int64_t stride, n;
     float *out; int accumulate;

@@ -12,12 +12,12 @@
 //             per-tile column sums / sums of squares of y in papc_bn_finalize_f32's [n_tiles][2][Cout] layout).
 //   backward  cc_bwd_kernel: ONE pass over (dz, y) in chunks of 128 rows of one cloud.  dY is formed on the fly from the layer's BN
 //             constants (as every backward kernel of the stack does), a chunk writes its dX rows, its partial dW_p and its partial column
-//             sums to slots of its own; cc_fold_kernel folds them in chunk order; cc_tail_kernel forms dW_g, d bias and dg from s.
+//             sums to slots of its own; cc_fold_kernel folds them in chunk order (fold.h); cc_tail_kernel forms dW_g, d bias and dg from s.
 //             No float atomics: two runs are bit-identical.
 // Products: v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation: the PAPC_GEMM_F32 arithmetic of papc_mlp_gemm_f32).  At
 // K = 64 the layer is bound by the [M, Cout] traffic of y and dY, not by the matrix rate.  The small per-cloud products are fmaf chains
 // in ascending index order.  Plain C++ loads and stores only.
-#include "common.h"
+#include "fold.h"
 
 namespace papc {
 
@@ -241,32 +241,20 @@ __global__ __launch_bounds__(CC_T) void cc_bwd_kernel(const float *__restrict__ 
     }
 }
 
-// dW_p[o][k] (into w's layout, ldw) = sum over the T = B * nch chunks, in order; s[b][o] = sum over cloud b's nch chunks, in order
+// dW_p[o][k] (into w's layout, ldw) = sum over the T = B * nch chunks; s[b][o] = sum over cloud b's nch chunks (fold.h: both in order from 0.f)
 __global__ __launch_bounds__(CC_T) void cc_fold_kernel(const float *__restrict__ part_w, const float *__restrict__ part_s, int B, int nch, int Cout,
                                                        float *__restrict__ dw, int64_t ldw, float *__restrict__ s)
 {
     const int64_t t = (int64_t)blockIdx.x * CC_T + threadIdx.x;
     const int64_t nw = (int64_t)Cout * CC_CP;
     if (t < nw) {
-        const int T = B * nch;
-        const float *p = part_w + t;
-        float a = 0.f;
-        int c = 0;
-        for (; c + 4 <= T; c += 4) {
-            const float v0 = p[(int64_t)c * nw], v1 = p[(int64_t)(c + 1) * nw], v2 = p[(int64_t)(c + 2) * nw], v3 = p[(int64_t)(c + 3) * nw];
-            a += v0; a += v1; a += v2; a += v3;
-        }
-        for (; c < T; ++c) a += p[(int64_t)c * nw];
-        dw[(t / CC_CP) * ldw + (t % CC_CP)] = a;
+        dw[(t / CC_CP) * ldw + (t % CC_CP)] = fold_in_order<4, FOLD_FROM_ZERO, float>(part_w, nw, B * nch, t);
         return;
     }
     const int64_t u = t - nw;
     if (u >= (int64_t)B * Cout) return;
     const int64_t b = u / Cout, o = u - b * Cout;
-    const float *p = part_s + b * nch * Cout + o;
-    float a = 0.f;
-    for (int c = 0; c < nch; ++c) a += p[(int64_t)c * Cout];
-    s[u] = a;
+    s[u] = fold_in_order<1, FOLD_FROM_ZERO, float>(part_s, Cout, nch, b * nch * Cout + o);
 }
 
 // from s [B, Cout]: dW_g[o][k] = sum_b s[b][o] g[b][k] (into w's layout at column Cp + k), dg[b][k] = sum_o s[b][o] W[o][Cp + k],

@@ -6,10 +6,10 @@
 //   forward   one launch: a workgroup owns a tile of one cloud's rows and stages T[b] (and for C = 64 the x tile) in LDS.
 //   backward  dX[b] = dY[b] . T[b]^T and dT[b] = X[b]^T . dY[b] from ONE pass over dY: the N rows of a cloud are split into chunks (at
 //             B = 32 there are too few clouds to fill the chip), each chunk writes its dX rows and its partial dT to a workspace slot of
-//             its own; a second launch folds the chunks' partials in chunk order.  No float atomics: two runs are bit-identical.
+//             its own; a second launch folds the chunks' partials in chunk order (fold.h).  No float atomics: two runs are bit-identical.
 // Arithmetic is plain fp32 VALU (the operands are tiny; the launches are latency-sized): every output is a k-ordered fmaf chain from
 // zero, compiled with -ffp-contract=off.  Plain C++ loads and stores only.
-#include "common.h"
+#include "fold.h"
 
 namespace papc {
 
@@ -156,16 +156,13 @@ __global__ __launch_bounds__(CT_T) void ct_bwd3_kernel(const float *__restrict__
     if (tid < 9) part[((int64_t)b * gridDim.x + chunk) * 9 + tid] = red[tid][0];
 }
 
-// ---- the fold: dT[b][e] = sum over chunks c (in order) of part[b][c][e] ----------------------------------------------------------------
+// ---- the fold: dT[b][e] = sum over chunks c of part[b][c][e] (fold.h: in order from the first chunk) ---------------------------------------
 __global__ __launch_bounds__(CT_T) void ct_fold_kernel(const float *__restrict__ part, int nch, int CC, int64_t total, float *__restrict__ dT)
 {
     const int64_t t = (int64_t)blockIdx.x * CT_T + threadIdx.x;
     if (t >= total) return;
     const int64_t b = t / CC, e = t - b * CC;
-    const float *p = part + b * nch * CC + e;
-    float s = p[0];
-    for (int c = 1; c < nch; ++c) s += p[(int64_t)c * CC];
-    dT[t] = s;
+    dT[t] = fold_in_order<1, FOLD_FROM_FIRST, float>(part, CC, nch, b * nch * CC + e);
 }
 
 }  // namespace papc

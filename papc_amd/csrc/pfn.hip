@@ -21,7 +21,7 @@
 // G is accumulated in float64 on the matrix pipe (v_mfma_f64_16x16x4_f64: products of fp32 values are exact in f64), since the
 // quadratic forms cancel: raw coordinates are O(70 m), a channel's spread O(1).  The only dense passes left are the Gram pass
 // (reads the 19 MB input once) and the apply pass.
-#include "common.h"
+#include "fold.h"
 
 namespace papc {
 
@@ -594,35 +594,16 @@ __global__ __launch_bounds__(64) void pfn_bwd_finalize_kernel(const float *__res
     pfn_bwd_finalize_body<false>(sums, M, w, C, gram, mean, invstd, scale, dgamma, dbeta, dw, flags);
 }
 
-// The fold of the sparse pass's partial rows (the summation order of reduce_partials_kernel, bn_ops.hip: 64 elements x 16 chunk lanes, 8 loads
-// in flight) with the finalize above as the last-arriving workgroup's tail: one launch instead of two.
+// The fold of the sparse pass's partial rows (fold.h: the 16-lane fold papc_reduce_partials_f32 runs, here with 32 loads in flight) with the
+// finalize above as the last-arriving workgroup's tail: one launch instead of two.
 __global__ __launch_bounds__(1024) void pfn_bwd_fold_finalize_kernel(const float *__restrict__ part, int n_chunks, int64_t n, float *sums, unsigned *ticket,
                                                                     double M, const float *w, int C, const double *gram, const float *mean,
                                                                     const float *invstd, const float *scale, float *dgamma, float *dbeta, float *dw, int flags)
 {
     __shared__ float red[16][64];
-    const int el = threadIdx.x & 63, cl = threadIdx.x >> 6;
-    const int64_t i = (int64_t)blockIdx.x * 64 + el;
-    float s = 0.f;
-    if (i < n) {
-        for (int t0 = cl; t0 < n_chunks; t0 += 16 * 32) {     // (32 loads in flight; the same summation order as with 8)
-            float v[32];
-#pragma unroll
-            for (int j = 0; j < 32; ++j) {
-                const int t = t0 + 16 * j;
-                v[j] = part[(int64_t)(t < n_chunks ? t : t0) * n + i];
-            }
-#pragma unroll
-            for (int j = 0; j < 32; ++j) s += (t0 + 16 * j < n_chunks) ? v[j] : 0.f;
-        }
-    }
-    red[cl][el] = s;
-    __syncthreads();
-    if (cl == 0 && i < n) {
-#pragma unroll
-        for (int g = 1; g < 16; ++g) s += red[g][el];
-        pfn_st(sums + i, s);
-    }
+    const int64_t i = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
+    float s;
+    if (fold_lanes<16, 32>(part, n, n_chunks, i, i < n, red, s)) pfn_st(sums + i, s);
     if (pfn_last_block(ticket)) pfn_bwd_finalize_body<true>(sums, M, w, C, gram, mean, invstd, scale, dgamma, dbeta, dw, flags);
 }
 

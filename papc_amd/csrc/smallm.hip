@@ -23,6 +23,7 @@
 //     partial store (dW).
 //
 // Six MFMA products per fp32 product, fp32 accumulate, smallest terms first: same arithmetic as the row kernels (<= 1e-5 parity).
+#include "fold.h"
 #include "mlp_loaders.h"
 
 namespace papc {
@@ -592,7 +593,7 @@ __global__ __launch_bounds__(256) void pg_final_kernel(const float *__restrict__
     }
 }
 
-// ---- split-K partials -> gradient (fixed order) --------------------------------------------------------------------------------
+// ---- split-K partials -> gradient (fold.h: the in-order fold from the first chunk) ----------------------------------------------
 struct FoldJob {
     const float *part; int nsplit; int64_t stride, n; float *out; int accumulate;
 };
@@ -604,19 +605,14 @@ __global__ __launch_bounds__(256) void pg_fold_kernel(FoldJobs jobs)
     const FoldJob jb = jobs.j[blockIdx.y];
     const int64_t n4 = jb.n >> 2;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n4; e += (int64_t)gridDim.x * 256) {
-        float4 s = ld4(jb.part + e * 4);
-        for (int t = 1; t < jb.nsplit; ++t) {
-            const float4 v = ld4(jb.part + t * jb.stride + e * 4);
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
+        float4 s = fold_in_order<1, FOLD_FROM_FIRST, float4>(jb.part, jb.stride, jb.nsplit, e * 4);
         float4 *o = reinterpret_cast<float4 *>(jb.out + e * 4);
-        if (jb.accumulate) { const float4 a = *o; s.x += a.x; s.y += a.y; s.z += a.z; s.w += a.w; }
+        if (jb.accumulate) s = fold_add(s, *o);
         *o = s;
     }
     if (blockIdx.x == 0) {           // ragged tail (n % 4 elements)
         for (int64_t e = (n4 << 2) + threadIdx.x; e < jb.n; e += 256) {
-            float s = jb.part[e];
-            for (int t = 1; t < jb.nsplit; ++t) s += jb.part[t * jb.stride + e];
+            const float s = fold_in_order<1, FOLD_FROM_FIRST, float>(jb.part, jb.stride, jb.nsplit, e);
             jb.out[e] = jb.accumulate ? jb.out[e] + s : s;
         }
     }
