@@ -93,6 +93,12 @@ def alloc_lists(B, N, G, K, device):
             torch.empty(cap + 3 * B * N, 4, device=device, dtype=torch.float32))
 
 
+def is_lists(t, _like=alloc_lists(1, 1, 1, 1, "cpu")):
+    """whether the tensors ``t`` are a point-list segment: the ranks, trailing sizes and dtypes of ``alloc_lists`` (prange [B*N, 2] int32, prow [cap]
+    int32, pmeta [., 4] float32)"""
+    return len(t) == len(_like) and all(x.dim() == y.dim() and x.shape[1:] == y.shape[1:] and x.dtype == y.dtype for x, y in zip(t, _like))
+
+
 def point_lists(xyz, new_xyz, idx, cplan=None, out=None):
     """xyz [B,N,3] (any strides), new_xyz [B,S,3], idx [B,S,K] int32, ``cplan`` = the grouping's CompactPlan when its stack runs compacted
     -> PointLists; ``out`` = optional preallocated tensors (``alloc_lists``) the kernel writes into."""
@@ -119,3 +125,49 @@ def stack_ok(M, K, couts):
         return False
     arr = (ctypes.c_int * len(couts))(*couts)
     return bool(_lib.load().papc_mlp_compact_ok(M, K, len(couts), arr))
+
+
+class StackPolicy:
+    """Whether one gather-add stack (a PointNetSetAbstraction, or one radius branch of a PointNetSetAbstractionMsg) runs compacted, and whether its
+    grouping gets point lists.  ``layer`` carries ``npoint``, ``training``, ``reference_quirks`` and the public switch ``compact``: None = decide once
+    from the data (the first sampling outside a graph capture measures how many of the nsample slots are padding copies; ``on`` keeps the answer),
+    True / False = forced.  The two layer kinds differ on purpose:
+      pad_width     the feature width must be >= 16 and a multiple of 4: MSG tests the width its branches pad to, SSG the width as it is;
+      padded_lists  SSG makes lists for a padded stack too (LISTS >= 2); MSG only ever for a compacted branch (LISTS >= 1);
+      keep_forced   MSG records a forced plan in ``on`` (its sample() and forward() read a branch's layout from that flag), SSG leaves it alone;
+      never         a group_all layer never compacts and has no lists."""
+
+    def __init__(self, layer, convs, nsample, pad_width, padded_lists, keep_forced, never=False):
+        self.layer, self.convs, self.nsample, self.on = layer, convs, nsample, None
+        self.padded_lists, self.keep_forced = padded_lists, keep_forced
+        D = convs[0].in_channels - 3
+        D += (-D) % 4 if pad_width else 0
+        self.wide = not never and D >= 16 and D % 4 == 0 and len(convs) >= 2       # a gather-add first layer the kernels take
+
+    def mode(self, B):
+        """None: this stack has no compacted flavour (or PAPC_COMPACT=0, or forced off); True / False: decided; "probe": to be measured"""
+        forced = self.layer.compact
+        if forced is False or not self.wide:
+            return None
+        if not stack_ok(B * self.layer.npoint * self.nsample, self.nsample, [c.out_channels for c in self.convs]):
+            return None
+        if forced is True or POLICY == "1":
+            return True
+        return "probe" if self.on is None else self.on
+
+    def plan(self, idx, out=None):
+        """the compacted layout of these ball-query lists, or None when the stack runs padded"""
+        mode = self.mode(idx.shape[0])
+        if not mode or (mode == "probe" and _lib._capturing()):     # undecided inside a capture: stay padded (a decision needs a host read)
+            return None
+        cp = plan(idx, out)
+        if mode == "probe":
+            self.on = cp.fraction() <= AUTO_MAX_FRACTION
+        elif self.keep_forced:
+            self.on = True
+        return cp if mode is True or self.on else None
+
+    def wants_lists(self, compacted, N):
+        """point lists are made for a training stack whose first layer can run as a gather-add, over clouds of N points the builder can hold"""
+        on = LISTS >= 1 if compacted else (self.padded_lists and LISTS >= 2)
+        return on and self.layer.training and self.wide and N <= MAX_LIST_POINTS and not self.layer.reference_quirks

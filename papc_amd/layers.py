@@ -19,8 +19,10 @@ import torch.nn as nn
 
 from . import _lib
 from . import functional as F_
+from .compact import StackPolicy, point_lists
 from .copyops import cat_copy, contiguous_copy, pad_cols
 from .mlp import StackSpec, shared_mlp_max
+from .plan import N_COMPACT, N_LISTS, N_XYZ_PRE, Cursor, Level
 
 
 def _stack_params(convs, bns):
@@ -68,40 +70,16 @@ class PointNetSetAbstraction(nn.Module):
         self.group_all = group_all
         self.reference_quirks = reference_quirks
         self.init_dist = init_dist   # the source initialises the FPS running distance with ones (:75)
-        # compacted stack (compact.py): None = decide once from the data (the first sampling outside a graph capture measures how many of the
-        # nsample slots are padding copies), True / False = forced
+        # compacted stack: None = decide once from the data, True / False = forced (compact.StackPolicy)
         self.compact = None
-        self._compact_on = None
+        self._policy = StackPolicy(self, self.mlp_convs, nsample, pad_width=False, padded_lists=True, keep_forced=False, never=group_all)
         if reference_quirks:
             for p in self.parameters():
                 p.requires_grad_(False)
 
-    def _compact_mode(self, B):
-        """None: this stack has no compacted flavour (or PAPC_COMPACT=0); True / False: decided; "probe": to be measured"""
-        from . import compact as C
-        convs = self.mlp_convs
-        D = convs[0].in_channels - 3
-        if self.group_all or self.compact is False or D < 16 or D % 4 or len(convs) < 2:
-            return None
-        if not C.stack_ok(B * self.npoint * self.nsample, self.nsample, [c.out_channels for c in convs]):
-            return None
-        if self.compact is True or C.POLICY == "1":
-            return True
-        return "probe" if self._compact_on is None else self._compact_on
-
-    def _compact_plan(self, idx, out=None):
-        """the compacted layout of these ball-query lists, or None when the layer runs padded"""
-        from . import compact as C
-        mode = self._compact_mode(idx.shape[0])
-        if mode is None or mode is False:
-            return None
-        if mode == "probe":
-            if _lib._capturing():          # undecided inside a capture: stay on the padded path (a decision needs a host read)
-                return None
-            cp = C.plan(idx, out)
-            self._compact_on = cp.fraction() <= C.AUTO_MAX_FRACTION
-            return cp if self._compact_on else None
-        return C.plan(idx, out)
+    @property
+    def _compact_on(self):
+        return self._policy.on
 
     def sample_fps(self, xyz, start_idx=None, out=None):
         """Farthest-point sampling alone (:143-144): xyz [B,3,N] -> new_xyz [B,S,3] (written into ``out`` when given).  The serial half of
@@ -116,9 +94,9 @@ class PointNetSetAbstraction(nn.Module):
 
     def sample(self, xyz, start_idx=None, out=None, new_xyz=None):
         """The weight-independent half of the layer (FPS + ball query, :143-145) on its own: xyz [B,3,N] ->
-        (new_xyz [B,S,3], idx [B,S,K] int32).  Lets a training loop run batch i+1's sampling on a side stream while
-        batch i's MLP kernels own the other CUs (FPS is a serial chain that occupies only B of the 256 CUs).
-        ``out`` = optional preallocated (new_xyz, idx) the kernels write straight into (no copies in a captured step);
+        (new_xyz [B,S,3], idx [B,S,K] int32, ...: the level's flat plan, plan.py).  Lets a training loop run batch i+1's sampling on a side
+        stream while batch i's MLP kernels own the other CUs (FPS is a serial chain that occupies only B of the 256 CUs).
+        ``out`` = optional previous result for the same shapes the kernels write straight into (no copies in a captured step);
         ``new_xyz`` = the centroids :meth:`sample_fps` already made for this xyz (no FPS here)."""
         if self.group_all:
             return None
@@ -126,61 +104,36 @@ class PointNetSetAbstraction(nn.Module):
         if xyz.dtype != torch.float32:
             xyz = xyz.float()
         skip = _diag_skip(self.npoint) if out is not None else ()      # (timing diagnostics: stages left out, their buffers stale)
+        w = Cursor(out)
+        o_xyz, o_idx = w.next(2) or (None, None)
         if new_xyz is None:
-            if "fps" in skip:
-                new_xyz = out[0]
-            else:
-                _, new_xyz = F_._fps_raw(xyz, self.npoint, start_idx, self.init_dist, new_xyz_out=None if out is None else out[0])
+            new_xyz = o_xyz if "fps" in skip else F_._fps_raw(xyz, self.npoint, start_idx, self.init_dist, new_xyz_out=o_xyz)[1]
         if "bq" in skip:
-            idx = out[1]
+            idx = o_idx
         else:
-            idx = F_._ball_query_raw([self.radius], [self.nsample], xyz, new_xyz, outs=None if out is None else [out[1]])[0]
+            idx = F_._ball_query_raw([self.radius], [self.nsample], xyz, new_xyz, outs=None if o_idx is None else [o_idx])[0]
+        w.put(new_xyz, idx)
         if self._xyz_first(xyz.shape[0]):
             # coordinates-only stack whose first layer runs through its input moments: the grouped centred coordinates and their
             # moments are weight-independent too (mlp.xyz_pregroup) -- part of the plan
             from .mlp import xyz_pregroup
-            if "xyzpre" in skip and len(out) >= 4:
-                return new_xyz, idx, out[2], out[3]
-            xc, gpart = xyz_pregroup(xyz, new_xyz, idx, out=None if (out is None or len(out) < 4) else (out[2], out[3]))
-            return new_xyz, idx, xc, gpart
-        if "compact" in skip and len(out) in (9, 12):
+            pre = w.next(N_XYZ_PRE)
+            if "xyzpre" not in skip or pre is None:
+                pre = xyz_pregroup(xyz, new_xyz, idx, out=pre)
+            return w.put(*pre)
+        # the compact plan and the grouping's point lists (the inverse index the gather-add backward sums over) are part of the plan too
+        bufs = w.next(N_COMPACT, then=(0, N_LISTS))
+        if "compact" in skip and bufs is not None:
             return tuple(out)
-        cp = self._compact_plan(idx, out=None if (out is None or len(out) not in (9, 12)) else tuple(out[2:9]))
-        # (new_xyz, idx[, cnt8, start, rows, cidx, seg_grp, wrow, coef][, prange, prow, pmeta]): the compact plan and the grouping's point
-        # lists (the inverse index the gather-add backward sums over) are part of the plan like the lists themselves
-        res = (new_xyz, idx) + (cp.tensors() if cp is not None else ())
-        if "lists" in skip and out is not None and len(out) == len(res) + 3:
-            return res + tuple(out[len(res):])
-        if self._wants_lists(xyz, cp):
-            from . import compact as _c
-            have = out is not None and len(out) == len(res) + 3
-            pl = _c.point_lists(xyz, new_xyz, idx, cp, out=tuple(out[len(res):]) if have else None)
-            res = res + pl.tensors()
-        return res
-
-    def _wants_lists(self, xyz, cplan):
-        """point lists are made for a training layer whose first layer can run as a gather-add (features present: decided by the stack plan) --
-        by default only when the stack runs compacted (compact.LISTS)"""
-        from . import compact as _c
-        D = self.mlp_convs[0].in_channels - 3
-        on = _c.LISTS >= 2 or (_c.LISTS == 1 and cplan is not None)
-        return (on and self.training and not self.group_all and D >= 16 and D % 4 == 0 and len(self.mlp_convs) >= 2
-                and xyz.shape[1] <= _c.MAX_LIST_POINTS and not self.reference_quirks)
-
-    @staticmethod
-    def _parse_plan(sampled, G, K):
-        """(new_xyz, idx, xyz_pre, CompactPlan, PointLists) from a :meth:`sample` result"""
-        from .compact import CompactPlan, PointLists
-        new_xyz, idx = sampled[0], sampled[1]
-        rest = tuple(sampled[2:])
-        xyz_pre = rest if len(rest) == 2 else None
-        cplan = plists = None
-        if len(rest) in (7, 10):
-            cplan = CompactPlan(rest[:7], G, K)
-            rest = rest[7:]
-        if len(rest) == 3:
-            plists = PointLists(rest, cplan is not None)
-        return new_xyz, idx, xyz_pre, cplan, plists
+        cp = self._policy.plan(idx, out=bufs)
+        if cp is not None:
+            w.put(*cp.tensors())
+        bufs = w.next(N_LISTS, then=(0,))
+        if "lists" in skip and bufs is not None:
+            return w.put(*bufs)
+        if self._policy.wants_lists(cp is not None, xyz.shape[1]):
+            w.put(*point_lists(xyz, new_xyz, idx, cp, out=bufs).tensors())
+        return w.res
 
     def _xyz_first(self, B):
         from .mlp import xyz_first_layer_ok
@@ -206,18 +159,16 @@ class PointNetSetAbstraction(nn.Module):
             idx = None
         else:                                                                   # sample_and_group :129-157
             S, K = self.npoint, self.nsample
-            xyz_pre = None
-            cplan = plists = None
             if sampled is not None:
-                new_xyz, idx, xyz_pre, cplan, plists = self._parse_plan(sampled, B * S, K)
+                lv = Level.parse(sampled, B * S, [K])
             else:
                 _, new_xyz = F_._fps_raw(xyz, S, start_idx, self.init_dist)
-                idx = F_._ball_query_raw([self.radius], [K], xyz, new_xyz)[0]
+                lv = Level(new_xyz, F_._ball_query_raw([self.radius], [K], xyz, new_xyz))
                 if feats is not None:
-                    cplan = self._compact_plan(idx)
-                    if self._wants_lists(xyz, cplan) and torch.is_grad_enabled():
-                        from . import compact as _c
-                        plists = _c.point_lists(xyz, new_xyz, idx, cplan)
+                    lv.cplans[0] = self._policy.plan(lv.idxs[0])
+                    if self._policy.wants_lists(lv.cplans[0] is not None, N) and torch.is_grad_enabled():
+                        lv.plists[0] = point_lists(xyz, new_xyz, lv.idxs[0], lv.cplans[0])
+            new_xyz, idx = lv.new_xyz, lv.idxs[0]
         params = _stack_params(self.mlp_convs, self.mlp_bns)
         if feats is not None:
             feats, params, D = _pad_features(feats, params, True)
@@ -225,10 +176,9 @@ class PointNetSetAbstraction(nn.Module):
                          cut_gather_grad=self.reference_quirks)
         spec.wt_table = wt_table
         if not self.group_all and feats is None:
-            spec.xyz_pre = xyz_pre
+            spec.xyz_pre = lv.xyz_pre
         if not self.group_all and feats is not None:
-            spec.compact = cplan
-            spec.plists = plists
+            spec.compact, spec.plists = lv.cplans[0], lv.plists[0]
         out = shared_mlp_max(spec, _bn_buffers(self.mlp_bns), xyz, new_xyz, feats, idx, params)   # :214-219
         new_points = out.view(B, S, -1).transpose(1, 2)                         # [B,D',S]
         # (group_all: new_xyz is the cached READ-ONLY zero centre of sample_and_group_all, :170 -- a clone here would put a copy kernel
@@ -284,75 +234,40 @@ class PointNetSetAbstractionMsg(nn.Module):
             self.bn_blocks.append(bns)
         self.reference_quirks = reference_quirks
         self.init_dist = init_dist
-        self.compact = None            # compacted branches (compact.py): None = decide once per branch from the data, True / False = forced
-        self._compact_on = {}
+        self.compact = None            # compacted branches: None = decide once per branch from the data, True / False = forced (compact.StackPolicy)
+        self._policies = [StackPolicy(self, convs, K, pad_width=True, padded_lists=False, keep_forced=True)
+                          for convs, K in zip(self.conv_blocks, nsample_list)]
         self.branch_streams = None     # radius branches on parallel streams: None = the process default (PAPC_MSG_STREAMS), True / False = this layer
         if reference_quirks:
             for p in self.parameters():
                 p.requires_grad_(False)
 
-    def _branch_compact_mode(self, i, B):
-        """None: branch i has no compacted flavour; True / False: decided; "probe": to be measured (see PointNetSetAbstraction)"""
-        from . import compact as C
-        convs = self.conv_blocks[i]
-        D = convs[0].in_channels - 3
-        Dp = D + ((-D) % 4)
-        if self.compact is False or Dp < 16 or len(convs) < 2:
-            return None
-        if not C.stack_ok(B * self.npoint * self.nsample_list[i], self.nsample_list[i], [c.out_channels for c in convs]):
-            return None
-        if self.compact is True or C.POLICY == "1":
-            return True
-        on = self._compact_on.get(i)
-        return "probe" if on is None else on
-
-    def _branch_plan(self, i, idx, out=None):
-        from . import compact as C
-        mode = self._branch_compact_mode(i, idx.shape[0])
-        if mode is None or mode is False:
-            return None
-        if mode == "probe":
-            if _lib._capturing():
-                return None
-            cp = C.plan(idx, out)
-            self._compact_on[i] = cp.fraction() <= C.AUTO_MAX_FRACTION
-            return cp if self._compact_on[i] else None
-        self._compact_on[i] = True      # forced (compact=True / PAPC_COMPACT=1): sample() and forward() read the branch's layout from this one flag
-        return C.plan(idx, out)
-
-    def _branch_wants_lists(self, i, N):
-        """point lists (compact.point_lists) for a compacted branch of a training layer: its gather-add backward as a segmented sum"""
-        from . import compact as C
-        D = self.conv_blocks[i][0].in_channels - 3
-        return (C.LISTS >= 1 and self.training and not self.reference_quirks and D + ((-D) % 4) >= 16 and len(self.conv_blocks[i]) >= 2
-                and N <= C.MAX_LIST_POINTS)
+    @property
+    def _compact_on(self):
+        return {i: p.on for i, p in enumerate(self._policies) if p.on is not None}
 
     def sample(self, xyz, start_idx=None, out=None):
         """The weight-independent half (one FPS, one ball-query scan for all radii, :258-262) on its own: xyz [B,3,N] ->
-        (new_xyz [B,S,3], idx_0 .. idx_{R-1} [B,S,K_r] int32, then per branch that runs compacted its 7 compact-plan tensors and -- for a
-        training layer -- the 3 point-list tensors of that layout).  ``out`` = a previous result of this method for the same shapes: the kernels
-        write into it."""
+        (new_xyz [B,S,3], idx_0 .. idx_{R-1} [B,S,K_r] int32, then per branch that runs compacted its compact-plan tensors and -- for a
+        training layer -- the point-list tensors of that layout; plan.py has the layout).  ``out`` = a previous result of this method for the
+        same shapes: the kernels write into it."""
         xyz = xyz.transpose(1, 2)
         if xyz.dtype != torch.float32:
             xyz = xyz.float()
-        R = len(self.radius_list)
-        _, new_xyz = F_._fps_raw(xyz, self.npoint, start_idx, self.init_dist, new_xyz_out=None if out is None else out[0])
-        idxs = F_._ball_query_raw(self.radius_list, self.nsample_list, xyz, new_xyz, outs=None if out is None else list(out[1:1 + R]))
-        res = [new_xyz] + list(idxs)
-        pos = 1 + R
-        for i in range(R):
-            forced = self._branch_compact_mode(i, xyz.shape[0]) is True
-            have = out is not None and (forced or self._compact_on.get(i) is True) and len(out) >= pos + 7
-            cp = self._branch_plan(i, idxs[i], out=tuple(out[pos:pos + 7]) if have else None)
+        B, N, _ = xyz.shape
+        w = Cursor(out)
+        o = w.next(1 + len(self.radius_list))
+        _, new_xyz = F_._fps_raw(xyz, self.npoint, start_idx, self.init_dist, new_xyz_out=None if o is None else o[0])
+        idxs = F_._ball_query_raw(self.radius_list, self.nsample_list, xyz, new_xyz, outs=None if o is None else list(o[1:]))
+        w.put(new_xyz, *idxs)
+        for pol, idx in zip(self._policies, idxs):
+            # (a branch that is still to be measured plans into fresh tensors: only a decided one knows that ``out`` holds its plan)
+            cp = pol.plan(idx, out=w.next(N_COMPACT) if pol.mode(B) is True else None)
             if cp is not None:
-                res += list(cp.tensors())
-                pos += 7
-                if self._branch_wants_lists(i, xyz.shape[1]):
-                    from . import compact as C
-                    have_l = out is not None and len(out) >= pos + 3
-                    res += list(C.point_lists(xyz, new_xyz, idxs[i], cp, out=tuple(out[pos:pos + 3]) if have_l else None).tensors())
-                    pos += 3
-        return tuple(res)
+                w.put(*cp.tensors())
+                if pol.wants_lists(True, N):
+                    w.put(*point_lists(xyz, new_xyz, idx, cp, out=w.next(N_LISTS)).tensors())
+        return w.res
 
     def forward(self, xyz, points, start_idx=None, sampled=None):
         xyz = xyz.transpose(1, 2)                                               # :252
@@ -365,30 +280,17 @@ class PointNetSetAbstractionMsg(nn.Module):
         D = 0 if feats is None else feats.shape[2]
         S = self.npoint
         R = len(self.radius_list)
-        cplans = [None] * R
-        plists = [None] * R
         if sampled is not None:
-            from .compact import CompactPlan, PointLists
-            new_xyz, idxs = sampled[0], list(sampled[1:1 + R])
-            pos = 1 + R
-            for i in range(R):
-                if self._compact_on.get(i) is True and self._branch_compact_mode(i, B) is True and len(sampled) >= pos + 7:
-                    cplans[i] = CompactPlan(tuple(sampled[pos:pos + 7]), B * S, self.nsample_list[i])
-                    pos += 7
-                    # (the lists are recognised by their shapes -- prange is [B*N, 2], pmeta [cap, 4] -- not by this layer's current mode: a plan
-                    # made in another mode parses all the same)
-                    if len(sampled) >= pos + 3 and sampled[pos].dim() == 2 and sampled[pos].shape[1] == 2 and sampled[pos + 2].dim() == 2:
-                        plists[i] = PointLists(tuple(sampled[pos:pos + 3]), True)
-                        pos += 3
+            lv = Level.parse(sampled, B * S, self.nsample_list, compacted=[p.on is True and p.mode(B) is True for p in self._policies])
         else:
             _, new_xyz = F_._fps_raw(xyz, S, start_idx, self.init_dist)             # :258 (one FPS for all radii)
-            idxs = F_._ball_query_raw(self.radius_list, self.nsample_list, xyz, new_xyz)   # :260-262, one scan
+            lv = Level(new_xyz, F_._ball_query_raw(self.radius_list, self.nsample_list, xyz, new_xyz))   # :260-262, one scan
             if feats is not None:
-                cplans = [self._branch_plan(i, idxs[i]) for i in range(R)]
+                lv.cplans = [p.plan(idx) for p, idx in zip(self._policies, lv.idxs)]
                 if torch.is_grad_enabled():
-                    from . import compact as C
-                    plists = [C.point_lists(xyz, new_xyz, idxs[i], cplans[i]) if (cplans[i] is not None and self._branch_wants_lists(i, N)) else None
-                              for i in range(R)]
+                    lv.plists = [point_lists(xyz, new_xyz, idx, cp) if (cp is not None and p.wants_lists(True, N)) else None
+                                 for p, idx, cp in zip(self._policies, lv.idxs, lv.cplans)]
+        new_xyz, idxs, cplans, plists = lv.new_xyz, lv.idxs, lv.cplans, lv.plists
         feats_in = feats
         padded = None
         if feats_in is not None and D % 4 != 0:          # (one padded copy of the features for all branches)
@@ -421,12 +323,7 @@ class PointNetSetAbstractionMsg(nn.Module):
                 # every tensor the branch reads was allocated on the caller's stream: tell the allocator the side stream uses it too, in the
                 # forward here and in the backward autograd replays on the same stream (a freed block is otherwise handed to the next
                 # main-stream allocation while a side-stream kernel may still be reading it)
-                shared = [xyz, new_xyz, idxs[i], feats_in, None if padded is None else padded[0]]
-                if cplans[i] is not None:
-                    shared += list(cplans[i].tensors())
-                if plists[i] is not None:
-                    shared += list(plists[i].tensors())
-                for t in shared:
+                for t in (xyz, new_xyz, idxs[i], feats_in, None if padded is None else padded[0]) + lv.branch(i):
                     if t is not None:
                         t.record_stream(side[i - 1])
                 with torch.cuda.stream(side[i - 1]):

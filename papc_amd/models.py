@@ -21,6 +21,7 @@ from . import _lib
 from . import head as _head
 from .copyops import cat_copy
 from .mlp import StackSpec, shared_mlp_max
+from .plan import new_xyz
 
 import os
 _FUSED_HEAD = os.environ.get("PAPC_NO_FUSED_HEAD") != "1"     # A/B switch: fused classifier head (head.py) vs the library-op chain
@@ -110,9 +111,9 @@ class PointNet2_SSG_Clas(nn.Module, _ClasHead):
         with torch.no_grad():
             o = out if out is not None else (None, None)
             if stage == "fps1":
-                return self.sa1.sample_fps(xyz, s[0], out=o[0][0])
-            p1 = self.sa1.sample(xyz, s[0], out=o[0], new_xyz=o[0][0] if stage == "rest" else None)
-            p2 = self.sa2.sample(p1[0].transpose(1, 2), s[1], out=o[1])
+                return self.sa1.sample_fps(xyz, s[0], out=new_xyz(o[0]))
+            p1 = self.sa1.sample(xyz, s[0], out=o[0], new_xyz=new_xyz(o[0]) if stage == "rest" else None)
+            p2 = self.sa2.sample(new_xyz(p1).transpose(1, 2), s[1], out=o[1])
         return p1, p2
 
     def forward(self, inputs, start_idx=None, plan=None, after_sa2=None, tap=None, after_sa3=None, labels=None, after_sa1=None):
@@ -445,9 +446,9 @@ class _PartSegBase(nn.Module):
         o = out if out is not None else (None, None, None, None)
         with torch.no_grad():
             p1 = self.sa1.sample(l0_xyz, s[0], out=o[0])
-            l1_xyz = p1[0].transpose(1, 2)
+            l1_xyz = new_xyz(p1).transpose(1, 2)
             p2 = self.sa2.sample(l1_xyz, s[1], out=o[1])
-            l2_xyz = p2[0].transpose(1, 2)
+            l2_xyz = new_xyz(p2).transpose(1, 2)
             n2 = self.fp2.plan(l1_xyz, l2_xyz, out=o[2])
             n1 = self.fp1.plan(l0_xyz, l1_xyz, out=o[3])
         return p1, p2, n2, n1
