@@ -18,8 +18,6 @@
 
 namespace papc {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
 template <int I, int N, class F>
 __device__ __forceinline__ void dw_sfor(F &&f)       // f(std::integral_constant<int, I>{}) for I in [I, N): compile-time indices
 {
@@ -244,7 +242,7 @@ __global__ __launch_bounds__(256, 2) void dw_kernel(DwArgs p)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Wave-specialised dW on the bf16 matrix pipe (fp32 operands as exact 3-way bf16 splits, see split3 in mlp_loaders.h).
+// Wave-specialised dW on the bf16 matrix pipe (fp32 operands as exact 3-way bf16 splits, see bf16x3.h).
 //
 // 16 waves per workgroup: 4 CONSUMER waves (2 x 2 over the <=128x128 output tile, NTO x NTI 32x32 accumulators each) that
 // only ds_read + MFMA, and 3 groups of 4 PRODUCER waves that only load, transform, split and write LDS.  A stage is 16
@@ -437,7 +435,6 @@ __global__ __launch_bounds__(768, 3) void dw_ws_kernel(DwArgs p)
         for (int t = 0; t < n_stages; ++t) {
             const unsigned long long c0 = p.dbg ? __builtin_readcyclecounter() : 0;
             const char *Yb = smem + (t & 1) * STAGE_B, *Xb = Yb + TO * ROWB;
-            constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};   // smallest terms first
 #pragma unroll
             for (int kb = 0; kb < RS / 16; ++kb) {
                 bf16x8 ya[NTO][3], xb[NTI][3];
@@ -457,7 +454,7 @@ __global__ __launch_bounds__(768, 3) void dw_ws_kernel(DwArgs p)
                     for (int a = 0; a < NTO; ++a)
 #pragma unroll
                         for (int b = 0; b < NTI; ++b)
-                            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ya[a][PA[tt]], xb[b][PB[tt]], acc[a][b], 0, 0, 0);
+                            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ya[a][BF16X3_PA[tt]], xb[b][BF16X3_PB[tt]], acc[a][b], 0, 0, 0);
             }
             const unsigned long long c1 = p.dbg ? __builtin_readcyclecounter() : 0;
             lds_barrier();
@@ -685,14 +682,6 @@ __global__ __launch_bounds__(512, 2) void dw_rows_kernel(DwArgs p)
             }
         }
     };
-    auto split8 = [&](const float (&vin)[8], bf16x8 (&pl)[3]) {
-        uint2 a0, a1, a2, b0, b1, b2;
-        split3(make_float4(vin[0], vin[1], vin[2], vin[3]), a0, a1, a2);
-        split3(make_float4(vin[4], vin[5], vin[6], vin[7]), b0, b1, b2);
-        pl[0] = __builtin_bit_cast(bf16x8, make_uint4(a0.x, a0.y, b0.x, b0.y));
-        pl[1] = __builtin_bit_cast(bf16x8, make_uint4(a1.x, a1.y, b1.x, b1.y));
-        pl[2] = __builtin_bit_cast(bf16x8, make_uint4(a2.x, a2.y, b2.x, b2.y));
-    };
     auto compute = [&](int kb, const Raw &w) {
         int kin0 = 0;
         if (DYMODE == A_DY_MAX) {
@@ -725,14 +714,13 @@ __global__ __launch_bounds__(512, 2) void dw_rows_kernel(DwArgs p)
             }
             split8(v, pb[b]);
         }
-        constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};   // smallest terms first
 #pragma unroll
         for (int t = 0; t < 6; ++t)
 #pragma unroll
             for (int a = 0; a < NTO; ++a)
 #pragma unroll
                 for (int b = 0; b < NTI; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[a][PA[t]], pb[b][PB[t]], acc[a][b], 0, 0, 0);
+                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[a][BF16X3_PA[t]], pb[b][BF16X3_PB[t]], acc[a][b], 0, 0, 0);
     };
 
     // this wave's blocks: wave, wave + 8, ...; the raw operands of the next PF - 1 blocks are in flight while one is computed (a ring of PF
@@ -931,12 +919,7 @@ __global__ __launch_bounds__(64 * NW, 2) void dw_rowsx_kernel(DwArgs p)
             if constexpr (CP) v[j] = fmaf(-wof(w, j), fmaf(kB, y - kmu, kA), ksc * pp);
             else v[j] = fmaf(ksc, pp, -fmaf(kB, y - kmu, kA));
         }
-        uint2 a0, a1, a2, b0, b1, b2;
-        split3(make_float4(v[0], v[1], v[2], v[3]), a0, a1, a2);
-        split3(make_float4(v[4], v[5], v[6], v[7]), b0, b1, b2);
-        pa[0] = __builtin_bit_cast(bf16x8, make_uint4(a0.x, a0.y, b0.x, b0.y));
-        pa[1] = __builtin_bit_cast(bf16x8, make_uint4(a1.x, a1.y, b1.x, b1.y));
-        pa[2] = __builtin_bit_cast(bf16x8, make_uint4(a2.x, a2.y, b2.x, b2.y));
+        split8(v, pa);
     };
     // mma: the staged x planes of a block against this wave's dY planes
     auto mma = [&](const bf16x8 (&pa)[3], const char *stg) {
@@ -946,12 +929,11 @@ __global__ __launch_bounds__(64 * NW, 2) void dw_rowsx_kernel(DwArgs p)
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
                 pb[b][pl] = *reinterpret_cast<const bf16x8 *>(stg + pl * PLB + (32 * b + l31) * CHS + hi * 16);
-        constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};   // smallest terms first
 #pragma unroll
         for (int t = 0; t < 6; ++t)
 #pragma unroll
             for (int b = 0; b < NTI; ++b)
-                acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[PA[t]], pb[b][PB[t]], acc[b], 0, 0, 0);
+                acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[BF16X3_PA[t]], pb[b][BF16X3_PB[t]], acc[b], 0, 0, 0);
     };
 
     // every wave walks ALL blocks of the chunk (it owns channels, not rows).  The HBM round trip (~2 us) is several blocks long (a block
@@ -980,14 +962,9 @@ __global__ __launch_bounds__(64 * NW, 2) void dw_rowsx_kernel(DwArgs p)
         auto pin = [](float &x) { asm volatile("" : "+v"(x)); };
         auto pin4 = [&](float4 &r) { pin(r.x); pin(r.y); pin(r.z); pin(r.w); };
         auto pinu = [](uint2 &u) { asm volatile("" : "+v"(u.x), "+v"(u.y)); };
-        auto level = [](float4 &r, uint2 &pl) {      // one level of the exact split: the leading bf16 of each value, and what is left
-            pl.x = pack_bf16x2(r.x, r.y); pl.y = pack_bf16x2(r.z, r.w);
-            r.x -= bf16_lo(pl.x); r.y -= bf16_hi(pl.x); r.z -= bf16_lo(pl.y); r.w -= bf16_hi(pl.y);
-        };
-        constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};   // smallest terms first
         dw_sfor<0, 24>([&](auto g_) {
             constexpr int g = decltype(g_)::value, t = g / NTI, bb = g % NTI;
-            acc[bb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pc[PA[t]], pb[bb][PB[t]], acc[bb], 0, 0, 0);
+            acc[bb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pc[BF16X3_PA[t]], pb[bb][BF16X3_PB[t]], acc[bb], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (g < 8) {
                 const float y = w.y[g];
@@ -999,12 +976,12 @@ __global__ __launch_bounds__(64 * NW, 2) void dw_rowsx_kernel(DwArgs p)
                 if constexpr (CP) v[g] = fmaf(-wof(w, g), fmaf(kB, y - kmu, kA), ksc * pp);
                 else v[g] = fmaf(ksc, pp, -fmaf(kB, y - kmu, kA));
                 pin(v[g]);
-            } else if constexpr (g == 8) { ra = make_float4(v[0], v[1], v[2], v[3]); level(ra, a0); pin4(ra); pinu(a0); }
-            else if constexpr (g == 9) { level(ra, a1); pin4(ra); pinu(a1); }
+            } else if constexpr (g == 8) { ra = make_float4(v[0], v[1], v[2], v[3]); split_level(ra, a0); pin4(ra); pinu(a0); }
+            else if constexpr (g == 9) { split_level(ra, a1); pin4(ra); pinu(a1); }
             else if constexpr (g == 10) {
-                a2.x = pack_bf16x2(ra.x, ra.y); a2.y = pack_bf16x2(ra.z, ra.w); rb = make_float4(v[4], v[5], v[6], v[7]); level(rb, b0);
+                a2.x = pack_bf16x2(ra.x, ra.y); a2.y = pack_bf16x2(ra.z, ra.w); rb = make_float4(v[4], v[5], v[6], v[7]); split_level(rb, b0);
                 pinu(a2); pin4(rb); pinu(b0);
-            } else if constexpr (g == 11) { level(rb, b1); pin4(rb); pinu(b1); }
+            } else if constexpr (g == 11) { split_level(rb, b1); pin4(rb); pinu(b1); }
             else if constexpr (g == 12) {
                 b2.x = pack_bf16x2(rb.x, rb.y); b2.y = pack_bf16x2(rb.z, rb.w);
                 pinu(b2);
@@ -1017,8 +994,8 @@ __global__ __launch_bounds__(64 * NW, 2) void dw_rowsx_kernel(DwArgs p)
                     rx.x = fmaxf(fmaf(xsc, wx.x[4 * h + 0], xsh), 0.f); rx.y = fmaxf(fmaf(xsc, wx.x[4 * h + 1], xsh), 0.f);
                     rx.z = fmaxf(fmaf(xsc, wx.x[4 * h + 2], xsh), 0.f); rx.w = fmaxf(fmaf(xsc, wx.x[4 * h + 3], xsh), 0.f);
                     pin4(rx);
-                } else if constexpr (step == 1) { level(rx, q0); pin4(rx); pinu(q0); }
-                else if constexpr (step == 2) { level(rx, q1); pin4(rx); pinu(q1); }
+                } else if constexpr (step == 1) { split_level(rx, q0); pin4(rx); pinu(q0); }
+                else if constexpr (step == 2) { split_level(rx, q1); pin4(rx); pinu(q1); }
                 else {
                     q2.x = pack_bf16x2(rx.x, rx.y); q2.y = pack_bf16x2(rx.z, rx.w);
                     char *dst = stgn + xc * CHS + xq * (2 * RPT) + 8 * h;
@@ -1172,12 +1149,7 @@ __global__ __launch_bounds__(512, 2) void dw_rows_max_kernel(DwMaxArgs p)
             float v[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) { v[j] = fmaxf(fmaf(xs[b], w.x[b][j], xh[b]), 0.f); xsum[b] += v[j]; }
-            uint2 a0, a1, a2, b0, b1, b2;
-            split3(make_float4(v[0], v[1], v[2], v[3]), a0, a1, a2);
-            split3(make_float4(v[4], v[5], v[6], v[7]), b0, b1, b2);
-            pb[b][0] = __builtin_bit_cast(bf16x8, make_uint4(a0.x, a0.y, b0.x, b0.y));
-            pb[b][1] = __builtin_bit_cast(bf16x8, make_uint4(a1.x, a1.y, b1.x, b1.y));
-            pb[b][2] = __builtin_bit_cast(bf16x8, make_uint4(a2.x, a2.y, b2.x, b2.y));
+            split8(v, pb[b]);
         }
         {   // the one-hot rows: the value's three planes, parked at row (argmax - kin0) of this lane's eight
             uint2 q0, q1, q2;
@@ -1198,14 +1170,13 @@ __global__ __launch_bounds__(512, 2) void dw_rows_max_kernel(DwMaxArgs p)
         bf16x8 pg[3];
 #pragma unroll
         for (int t = 0; t < 3; ++t) pg[t] = yb ? pb[1][t] : pb[0][t];
-        constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};   // smallest terms first
 #pragma unroll
         for (int t = 0; t < 6; ++t)
 #pragma unroll
             for (int b = 0; b < NTI; ++b) {
-                acc[0][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[0][PA[t]], pb[b][PB[t]], acc[0][b], 0, 0, 0);
-                acc[1][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[1][PA[t]], pb[b][PB[t]], acc[1][b], 0, 0, 0);
-                acc[2][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pg[PA[t]], pb[b][PB[t]], acc[2][b], 0, 0, 0);
+                acc[0][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[0][BF16X3_PA[t]], pb[b][BF16X3_PB[t]], acc[0][b], 0, 0, 0);
+                acc[1][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[1][BF16X3_PA[t]], pb[b][BF16X3_PB[t]], acc[1][b], 0, 0, 0);
+                acc[2][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pg[BF16X3_PA[t]], pb[b][BF16X3_PB[t]], acc[2][b], 0, 0, 0);
             }
     };
 

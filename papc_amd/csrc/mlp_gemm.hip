@@ -71,7 +71,7 @@ __device__ __forceinline__ float4 mask_w4(const GemmArgs &p, int n, int k, float
 // the iteration and drain under the next stage's MFMAs (the barrier does not wait for them: lds_barrier()).
 //
 // BF3 = true: the operands are split into three bf16 planes when they are written to LDS and the products run on
-// v_mfma_f32_32x32x16_bf16 (six per 32x32x16 block, see split3 in mlp_loaders.h) -- fp32 accuracy at 2.7x the fp32 matrix
+// v_mfma_f32_32x32x16_bf16 (six per 32x32x16 block, see bf16x3.h) -- fp32 accuracy at 2.7x the fp32 matrix
 // rate.  A stage is then one 16-wide k block: LDS rows are [plane0 | plane1 | plane2] x 32 B + 16 B pad = 112 B (7 x 16 B,
 // odd -> the 16-lane groups of a ds_read_b128 hit 16 distinct 16-B slots); a lane's 16-B read at plane*32 + 16*(lane>>5) is
 // its 8 consecutive k of row lane&31, exactly the instruction's A/B operand.  BF3 = false is the exact fp32 path
@@ -286,8 +286,6 @@ __global__ __launch_bounds__((1 + WS) * WGM * WGN * 64, WS ? (1 + WS) : WGM * WG
     auto mfma_stage = [&](int buf, int kc_c) {
         if (BF3) {
             const char *Ab = reinterpret_cast<const char *>(smem + buf * STAGE), *Wb = Ab + BM * ROWB;
-            // smallest terms first; consecutive MFMAs go to different accumulators
-            constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
 #pragma unroll
             for (int kb = 0; kb < KB; ++kb) {
                 bf16x8 af[WM][3], bq[WN][3];
@@ -301,14 +299,15 @@ __global__ __launch_bounds__((1 + WS) * WGM * WGN * 64, WS ? (1 + WS) : WGM * WG
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl)
                         bq[wn][pl] = *reinterpret_cast<const bf16x8 *>(Wb + ((wgn * WN + wn) * 32 + l31) * ROWB + pl * PLB + kb * 32 + hi * 16);
+                // product t = BF16X3_PA[t] x BF16X3_PB[t] (smallest terms first); consecutive MFMAs go to different accumulators
 #pragma unroll
                 for (int t = 0; t < 6; ++t)
 #pragma unroll
                     for (int wm = 0; wm < WM; ++wm)
 #pragma unroll
                         for (int wn = 0; wn < WN; ++wn)
-                            acc[wm][wn] = TL ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq[wn][PB[t]], af[wm][PA[t]], acc[wm][wn], 0, 0, 0)
-                                             : __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[wm][PA[t]], bq[wn][PB[t]], acc[wm][wn], 0, 0, 0);
+                            acc[wm][wn] = TL ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq[wn][BF16X3_PB[t]], af[wm][BF16X3_PA[t]], acc[wm][wn], 0, 0, 0)
+                                             : __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[wm][BF16X3_PA[t]], bq[wn][BF16X3_PB[t]], acc[wm][wn], 0, 0, 0);
             }
         } else {
             const float *As = smem + buf * STAGE, *Ws = As + BM * LDT;

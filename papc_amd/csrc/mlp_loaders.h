@@ -15,7 +15,7 @@
 //   VEC = false: element-wise predicated loads for ragged shapes (correct for anything, slow).
 // fetch_a4 only issues loads (raw registers); finish_a4 does the arithmetic once they have landed.
 #pragma once
-#include "common.h"
+#include "bf16x3.h"
 
 namespace papc {
 
@@ -293,48 +293,6 @@ __device__ __forceinline__ float4 finish_a4(const ASrc &a, const RowCtx &r, int 
     }
     if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);
     return v;
-}
-
-// ---- fp32 on the bf16 matrix pipe: exact 3-way split.
-// x = x1 + x2 + x3 with x1 = bf16(x), x2 = bf16(x - x1), x3 = bf16(x - x1 - x2) (round-to-nearest-even each; the
-// subtractions are exact in fp32).  Three 8-bit significands cover the 24-bit fp32 significand, so the split is exact
-// (up to underflow of the tails), and a product a*b is recovered as the six bf16 products
-//   a1*b1 + (a1*b2 + a2*b1) + (a1*b3 + a2*b2 + a3*b1)
-// accumulated in fp32 by v_mfma_f32_32x32x16_bf16; the dropped terms (a2*b3, a3*b2, a3*b3) are below 2^-26 |a*b|,
-// i.e. under the rounding error of a single fp32 multiply-add.  6 MFMAs of 32 cycles per 32x32x16 block against
-// 8 x 64 cycles of v_mfma_f32_32x32x2_f32 for the same block: 2.7x the fp32 matrix rate at fp32 accuracy
-// (tools/probe/mfma_bf16_layout.hip measures 6.5e-8 max |err| / sum|a_k b_k| vs 1.5e-7 for the fp32 fma chain).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float floatx2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pack_bf16x2(float a, float b)  // -> v_cvt_pk_bf16_f32 (a in the low half)
-{
-    return __builtin_bit_cast(unsigned, __builtin_convertvector((floatx2_t){a, b}, bf16x2_t));
-}
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-
-// planes p0 (leading), p1, p2 of four consecutive-k values, each as 4 packed bf16 (8 bytes)
-#ifndef PAPC_SPLIT_PK
-#define PAPC_SPLIT_PK 0   // 1: the two exact subtractions of a pair as one v_pk_add_f32 -- measured SLOWER in the LDS-staged kernels (dW family 0.85 -> 0.90 ms/step: the producers pay moves to form aligned register pairs); the row-streaming kernel, whose pairs are natural, uses its own split3_pair
-#endif
-__device__ __forceinline__ void split3(float4 v, uint2 &p0, uint2 &p1, uint2 &p2)
-{
-#if PAPC_SPLIT_PK
-    floatx2_t a = {v.x, v.y}, b = {v.z, v.w};
-    p0.x = pack_bf16x2(a.x, a.y); p0.y = pack_bf16x2(b.x, b.y);
-    a = a - floatx2_t{bf16_lo(p0.x), bf16_hi(p0.x)}; b = b - floatx2_t{bf16_lo(p0.y), bf16_hi(p0.y)};
-    p1.x = pack_bf16x2(a.x, a.y); p1.y = pack_bf16x2(b.x, b.y);
-    a = a - floatx2_t{bf16_lo(p1.x), bf16_hi(p1.x)}; b = b - floatx2_t{bf16_lo(p1.y), bf16_hi(p1.y)};
-    p2.x = pack_bf16x2(a.x, a.y); p2.y = pack_bf16x2(b.x, b.y);
-#else
-    p0.x = pack_bf16x2(v.x, v.y); p0.y = pack_bf16x2(v.z, v.w);
-    v.x -= bf16_lo(p0.x); v.y -= bf16_hi(p0.x); v.z -= bf16_lo(p0.y); v.w -= bf16_hi(p0.y);
-    p1.x = pack_bf16x2(v.x, v.y); p1.y = pack_bf16x2(v.z, v.w);
-    v.x -= bf16_lo(p1.x); v.y -= bf16_hi(p1.x); v.z -= bf16_lo(p1.y); v.w -= bf16_hi(p1.y);
-    p2.x = pack_bf16x2(v.x, v.y); p2.y = pack_bf16x2(v.z, v.w);
-#endif
 }
 
 }  // namespace papc

@@ -16,7 +16,7 @@
 //     goes global -> VGPR directly (each 128-byte line is fetched once; both halves of a row are touched by the same instruction
 //     pair), is transformed (BN+ReLU of the previous layer / the BN+ReLU+max backward) and split in registers, and meets the
 //     weight fragments read from LDS in v_mfma_f32_32x32x16_bf16 (six products per block, fp32 accumulate: the exact 3-way split
-//     of mlp_loaders.h).  No A tile in LDS, no transposes.
+//     of bf16x3.h).  No A tile in LDS, no transposes.
 //   * Waves are independent streams: 8 per CU (2 per SIMD), each with its own prefetch -- the operand loads of k chunk c + 2 are
 //     issued when chunk c has been consumed, into the registers it frees, and waited for with a COUNTED s_waitcnt (only the
 //     younger chunk's loads may remain outstanding; loads return in order, so `vmcnt(#younger loads)` is exact).  The loads are
@@ -86,17 +86,7 @@ struct StreamGeo {
 #ifndef PAPC_STREAM_PK
 #define PAPC_STREAM_PK 1
 #endif
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-// three bf16 planes of one pair: x = p0 + p1 + p2 exactly (see split3 in mlp_loaders.h)
-__device__ __forceinline__ void split3_pair(f32x2 x, unsigned &p0, unsigned &p1, unsigned &p2)
-{
-    p0 = pack_bf16x2(x.x, x.y);
-    x = x - f32x2{bf16_lo(p0), bf16_hi(p0)};
-    p1 = pack_bf16x2(x.x, x.y);
-    x = x - f32x2{bf16_lo(p1), bf16_hi(p1)};
-    p2 = pack_bf16x2(x.x, x.y);
-}
+__device__ __forceinline__ floatx2_t pk_fma(floatx2_t a, floatx2_t b, floatx2_t c) { return __builtin_elementwise_fma(a, b, c); }
 
 // CP (dX of a compacted stack: DY operands, STORE_RED epilogue): per-row weight w in the BatchNorm-backward term, dy = sc p - w (A + B' (y - mean));
 // DY_MAX: the row's group comes from seg_grp (ragged groups), argmax holds absolute rows.  The weight of tile j + 1 and the group of tile
@@ -369,10 +359,10 @@ __global__ __launch_bounds__(NWT * 64, NWT / 4) void stream_kernel(GemmArgs p, S
 // (plain fmas: the packed form needs the row's coordinate broadcast into both halves -- hipcc encodes that as v_pk_fma_f32 with
             // op_sel / op_sel_hi on the (x, y) register pair, and that instruction returned wrong values for a varying ~15 % of the rows
             // on gfx950, ROCm 7.2: tools/probe/dbg_xyz2.py; the natural-pair pk_fma of the other operand flavours is unaffected)
-            f32x2 t;
+            floatx2_t t;
             t.x = fmaf(c[2][h][i], xv.z, fmaf(c[1][h][i], xv.y, fmaf(c[0][h][i], xv.x, c[3][h][i])));
             t.y = fmaf(c[2][h][i + 1], xv.z, fmaf(c[1][h][i + 1], xv.y, fmaf(c[0][h][i + 1], xv.x, c[3][h][i + 1])));
-            split3_pair(f32x2{fmaxf(t.x, 0.f), fmaxf(t.y, 0.f)}, q0[j], q1[j], q2[j]);
+            split3_pair(floatx2_t{fmaxf(t.x, 0.f), fmaxf(t.y, 0.f)}, q0[j], q1[j], q2[j]);
         }
         bf16x8 af[3];
         af[0] = __builtin_bit_cast(bf16x8, make_uint4(q0[0], q0[1], q0[2], q0[3]));
@@ -384,12 +374,11 @@ __global__ __launch_bounds__(NWT * 64, NWT / 4) void stream_kernel(GemmArgs p, S
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
                 bq[wn][pl] = *reinterpret_cast<const bf16x8 *>(wl + wn * 32 * ROWB + pl * 2 * K + kb * 32);
-        constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
 #pragma unroll
         for (int t = 0; t < 6; ++t)
 #pragma unroll
             for (int wn = 0; wn < WN; ++wn)
-                acc[wn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PA[t]], bq[wn][PB[t]], acc[wn], 0, 0, 0);
+                acc[wn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[BF16X3_PA[t]], bq[wn][BF16X3_PB[t]], acc[wn], 0, 0, 0);
     };
 
     // MFMAs of chunk `ci` from buffer `bi`
@@ -400,15 +389,15 @@ __global__ __launch_bounds__(NWT * 64, NWT / 4) void stream_kernel(GemmArgs p, S
             bf16x8 af[3];
 #if PAPC_STREAM_PK
             {
-                f32x2 v2[4];   // pairs (k, k+1): r[0] = k 0..3, r[1] = k 4..7 of this lane's half block
+                floatx2_t v2[4];   // pairs (k, k+1): r[0] = k 0..3, r[1] = k 4..7 of this lane's half block
                 if constexpr (AMODE == A_PLAIN) {
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) v2[j] = f32x2{r[j >> 1][2 * (j & 1)], r[j >> 1][2 * (j & 1) + 1]};
+                    for (int j = 0; j < NJ; ++j) v2[j] = floatx2_t{r[j >> 1][2 * (j & 1)], r[j >> 1][2 * (j & 1) + 1]};
                 } else if constexpr (MC && kb < KS) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int h = j >> 1, i = 2 * (j & 1);
-                        v2[j] = f32x2{(__float_as_int(r[2 + h][i]) == kin) ? r[h][i] : 0.f, (__float_as_int(r[2 + h][i + 1]) == kin) ? r[h][i + 1] : 0.f};
+                        v2[j] = floatx2_t{(__float_as_int(r[2 + h][i]) == kin) ? r[h][i] : 0.f, (__float_as_int(r[2 + h][i + 1]) == kin) ? r[h][i + 1] : 0.f};
                     }
                 } else if constexpr (AMODE == A_BNRELU || MC) {
                     const f32x4 s0 = *reinterpret_cast<const f32x4 *>(cl + kb * 64), s1 = *reinterpret_cast<const f32x4 *>(cl + kb * 64 + 16);
@@ -417,8 +406,8 @@ __global__ __launch_bounds__(NWT * 64, NWT / 4) void stream_kernel(GemmArgs p, S
                     for (int j = 0; j < NJ; ++j) {
                         const int h = j >> 1, i = 2 * (j & 1);
                         const f32x4 sc = h ? s1 : s0, sh = h ? h1 : h0;
-                        const f32x2 t = pk_fma(f32x2{sc[i], sc[i + 1]}, f32x2{r[h][i], r[h][i + 1]}, f32x2{sh[i], sh[i + 1]});
-                        v2[j] = f32x2{fmaxf(t.x, 0.f), fmaxf(t.y, 0.f)};
+                        const floatx2_t t = pk_fma(floatx2_t{sc[i], sc[i + 1]}, floatx2_t{r[h][i], r[h][i + 1]}, floatx2_t{sh[i], sh[i + 1]});
+                        v2[j] = floatx2_t{fmaxf(t.x, 0.f), fmaxf(t.y, 0.f)};
                     }
                 } else {
                     f32x4 c[5][2];
@@ -431,32 +420,32 @@ __global__ __launch_bounds__(NWT * 64, NWT / 4) void stream_kernel(GemmArgs p, S
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) {
                         const int h = j >> 1, i = 2 * (j & 1);
-                        const f32x2 y = f32x2{r[h][i], r[h][i + 1]};
-                        f32x2 dz = f32x2{r[2 + h][i], r[2 + h][i + 1]};
+                        const floatx2_t y = floatx2_t{r[h][i], r[h][i + 1]};
+                        floatx2_t dz = floatx2_t{r[2 + h][i], r[2 + h][i + 1]};
                         if constexpr (AMODE == A_DY_MAX) {
                             dz.x = (__float_as_int(r[4 + h][i]) == kin) ? dz.x : 0.f;
                             dz.y = (__float_as_int(r[4 + h][i + 1]) == kin) ? dz.y : 0.f;
                         }
-                        f32x2 c0 = f32x2{0.f, 0.f}, pp = dz;
+                        floatx2_t c0 = floatx2_t{0.f, 0.f}, pp = dz;
                         if constexpr (!PS) {
-                            c0 = f32x2{c[0][h][i], c[0][h][i + 1]};
-                            const f32x2 z = pk_fma(c0, y, f32x2{c[1][h][i], c[1][h][i + 1]});
-                            pp = f32x2{z.x > 0.f ? dz.x : 0.f, z.y > 0.f ? dz.y : 0.f};
+                            c0 = floatx2_t{c[0][h][i], c[0][h][i + 1]};
+                            const floatx2_t z = pk_fma(c0, y, floatx2_t{c[1][h][i], c[1][h][i + 1]});
+                            pp = floatx2_t{z.x > 0.f ? dz.x : 0.f, z.y > 0.f ? dz.y : 0.f};
                         }
                         if constexpr (CP) {
-                            const f32x2 t = pk_fma(f32x2{c[4][h][i], c[4][h][i + 1]}, y - f32x2{c[2][h][i], c[2][h][i + 1]}, f32x2{c[3][h][i], c[3][h][i + 1]});
+                            const floatx2_t t = pk_fma(floatx2_t{c[4][h][i], c[4][h][i + 1]}, y - floatx2_t{c[2][h][i], c[2][h][i + 1]}, floatx2_t{c[3][h][i], c[3][h][i + 1]});
                             // PS: dz IS scale * p at the group's argmax row (the reduction that made the BN-backward sums formed the same product of
                             // the same two floats): what the other path computes as c0 * pp
-                            if constexpr (PS) v2[j] = pk_fma(f32x2{wcur, wcur}, t, dz);
-                            else v2[j] = pk_fma(f32x2{wcur, wcur}, t, c0 * pp);
+                            if constexpr (PS) v2[j] = pk_fma(floatx2_t{wcur, wcur}, t, dz);
+                            else v2[j] = pk_fma(floatx2_t{wcur, wcur}, t, c0 * pp);
                         } else {
-                            const f32x2 inner = pk_fma(c0, pp, -f32x2{c[3][h][i], c[3][h][i + 1]});
-                            v2[j] = pk_fma(-f32x2{c[4][h][i], c[4][h][i + 1]}, y - f32x2{c[2][h][i], c[2][h][i + 1]}, inner);
+                            const floatx2_t inner = pk_fma(c0, pp, -floatx2_t{c[3][h][i], c[3][h][i + 1]});
+                            v2[j] = pk_fma(-floatx2_t{c[4][h][i], c[4][h][i + 1]}, y - floatx2_t{c[2][h][i], c[2][h][i + 1]}, inner);
                         }
                     }
                 }
                 if constexpr (NJ == 2) {      // (partial block: the upper half-wave holds a copy of the same four channels -- its k does not exist)
-                    if (hi) { v2[0] = f32x2{0.f, 0.f}; v2[1] = f32x2{0.f, 0.f}; }
+                    if (hi) { v2[0] = floatx2_t{0.f, 0.f}; v2[1] = floatx2_t{0.f, 0.f}; }
                 }
                 unsigned q0[4], q1[4], q2[4];
 #pragma unroll
@@ -500,12 +489,7 @@ __global__ __launch_bounds__(NWT * 64, NWT / 4) void stream_kernel(GemmArgs p, S
                         v[4 * h + i] = fmaf(-c[4][h][i], y - c[2][h][i], fmaf(c[0][h][i], pp, -c[3][h][i]));
                     }
             }
-            uint2 a0, a1, a2, b0, b1, b2;
-            split3(make_float4(v[0], v[1], v[2], v[3]), a0, a1, a2);
-            split3(make_float4(v[4], v[5], v[6], v[7]), b0, b1, b2);
-            af[0] = __builtin_bit_cast(bf16x8, make_uint4(a0.x, a0.y, b0.x, b0.y));
-            af[1] = __builtin_bit_cast(bf16x8, make_uint4(a1.x, a1.y, b1.x, b1.y));
-            af[2] = __builtin_bit_cast(bf16x8, make_uint4(a2.x, a2.y, b2.x, b2.y));
+            split8(v, af);
 #endif
             bf16x8 bq[WN][3];
 #pragma unroll
@@ -513,13 +497,12 @@ __global__ __launch_bounds__(NWT * 64, NWT / 4) void stream_kernel(GemmArgs p, S
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
                     bq[wn][pl] = *reinterpret_cast<const bf16x8 *>(((CB && wn == TB) ? wlb : wl + wn * 32 * ROWB) + pl * 2 * K + kb * 32);
-            // smallest terms first; consecutive MFMAs go to different accumulators
-            constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
+            // product t = BF16X3_PA[t] x BF16X3_PB[t] (smallest terms first); consecutive MFMAs go to different accumulators
 #pragma unroll
             for (int t = 0; t < 6; ++t)
 #pragma unroll
                 for (int wn = 0; wn < WN; ++wn)
-                    acc[wn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PA[t]], bq[wn][PB[t]], acc[wn], 0, 0, 0);
+                    acc[wn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[BF16X3_PA[t]], bq[wn][BF16X3_PB[t]], acc[wn], 0, 0, 0);
         }
     };
     auto compute = [&](auto bi_, auto ci_) {

@@ -21,6 +21,7 @@
 // G is accumulated in float64 on the matrix pipe (v_mfma_f64_16x16x4_f64: products of fp32 values are exact in f64), since the
 // quadratic forms cancel: raw coordinates are O(70 m), a channel's spread O(1).  The only dense passes left are the Gram pass
 // (reads the 19 MB input once) and the apply pass.
+#include "bf16x3.h"
 #include "fold.h"
 
 namespace papc {
@@ -334,41 +335,11 @@ __global__ __launch_bounds__(64 * WAVES) void pfn_kernel(PfnArgs a)
 
 // ---- apply pass on the bf16 matrix pipe -------------------------------------------------------------------------------
 // y [T, C] = X [T, 9] W^T for one pillar is 4 row tiles x 2 column tiles of v_mfma_f32_32x32x16_bf16 with the fp32 operands as
-// exact 3-way bf16 splits (6 products, fp32 accumulate: mlp_loaders.h).  K = 9 pads to ONE 16-wide k block: lane (row = lane & 31,
+// exact 3-way bf16 splits (6 products, fp32 accumulate: bf16x3.h).  K = 9 pads to ONE 16-wide k block: lane (row = lane & 31,
 // half = lane >> 5) feeds channels 0..7 / 8..15 of its row straight from the decorated LDS slab; W^T lives in registers for the
 // whole kernel.  The accumulator layout (lane = output channel, 16 rows per lane) is exactly what BN + ReLU + max over the T rows
 // want: z = fma(scale, y, shift) and a running (max, first row) per lane, one cross-half merge per pillar.  The lanes-are-channels
 // VALU form of this pass (pfn_kernel<PFN_APPLY>) spends 19 instructions per row and channel-wave; this one ~6.
-typedef __bf16 pfn_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 pfn_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float pfn_f32x2 __attribute__((ext_vector_type(2)));
-typedef float pfn_f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ unsigned pfn_pack2(float a, float b)
-{
-    return __builtin_bit_cast(unsigned, __builtin_convertvector((pfn_f32x2){a, b}, pfn_bf16x2));
-}
-// three bf16 planes of 8 consecutive-k values: v = pl[0] + pl[1] + pl[2] exactly
-__device__ __forceinline__ void pfn_split8(const float (&vin)[8], pfn_bf16x8 (&pl)[3])
-{
-    float v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = vin[i];
-    unsigned q[3][4];
-#pragma unroll
-    for (int lvl = 0; lvl < 3; ++lvl) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const unsigned u = pfn_pack2(v[2 * j], v[2 * j + 1]);
-            q[lvl][j] = u;
-            v[2 * j] -= __uint_as_float(u << 16);
-            v[2 * j + 1] -= __uint_as_float(u & 0xffff0000u);
-        }
-    }
-#pragma unroll
-    for (int lvl = 0; lvl < 3; ++lvl) pl[lvl] = __builtin_bit_cast(pfn_bf16x8, make_uint4(q[lvl][0], q[lvl][1], q[lvl][2], q[lvl][3]));
-}
-
 __global__ __launch_bounds__(64 * PFN_WAVES) void pfn_apply_mfma_kernel(PfnArgs a)
 {
     __shared__ __attribute__((aligned(16))) float smem[PFN_WAVES * PFN_TMAX * PFN_LD];
@@ -377,7 +348,7 @@ __global__ __launch_bounds__(64 * PFN_WAVES) void pfn_apply_mfma_kernel(PfnArgs 
     float *rows = smem + wave * PFN_TMAX * PFN_LD;
 
     // B operand: lane (n = l31, half) holds W[32 wn + n][8 half .. 8 half + 7]  (k >= 9 and channels >= C are zero)
-    pfn_bf16x8 bq[2][3];
+    bf16x8 bq[2][3];
     float sc[2], sh[2];
 #pragma unroll
     for (int wn = 0; wn < 2; ++wn) {
@@ -388,11 +359,10 @@ __global__ __launch_bounds__(64 * PFN_WAVES) void pfn_apply_mfma_kernel(PfnArgs 
             const int k = 8 * hi + j;
             wv[j] = (c < a.C && k < 9) ? a.w[c * 9 + k] : 0.f;
         }
-        pfn_split8(wv, bq[wn]);
+        split8(wv, bq[wn]);
         sc[wn] = c < a.C ? a.scale[c] : 0.f;
         sh[wn] = c < a.C ? a.shift[c] : 0.f;
     }
-    constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};   // smallest terms first
 
     PfnRaw nxt = {};
     int nv2 = 0;
@@ -423,16 +393,15 @@ __global__ __launch_bounds__(64 * PFN_WAVES) void pfn_apply_mfma_kernel(PfnArgs 
             float4 x1 = *reinterpret_cast<const float4 *>(rows + (32 * t + l31) * PFN_LD + 4);
             if (hi) x1 = make_float4(0.f, 0.f, 0.f, 0.f);
             const float xv[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-            pfn_bf16x8 af[3];
-            pfn_split8(xv, af);
+            bf16x8 af[3];
+            split8(xv, af);
             const bool full = 32 * (t + 1) <= a.T;
 #pragma unroll
             for (int wn = 0; wn < 2; ++wn) {
-                pfn_f32x16 acc;
+                floatx16 acc;
 #pragma unroll
                 for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-#pragma unroll
-                for (int m = 0; m < 6; ++m) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PA[m]], bq[wn][PB[m]], acc, 0, 0, 0);
+                acc = mfma_bf16x3(af, bq[wn], acc);
                 // C/D layout: column = l31, row = (q & 3) + 8 (q >> 2) + 4 half -- ascending in q
                 if (full) {
 #pragma unroll

@@ -11,7 +11,7 @@
 //   * prep kernels apply the elementwise part once per element (concat of sample_and_group_all; BN+ReLU of the previous layer with
 //     the batch statistics folded from the producer's per-tile partials in the prologue; the BN/ReLU/max backward dY with its two
 //     per-channel constants folded the same way), split the result into the three bf16 planes of the exact fp32 product
-//     (mlp_loaders.h: x = p0 + p1 + p2) and store them in MFMA FRAGMENT ORDER: a (32-row block, 16-wide k block, plane) fragment is
+//     (bf16x3.h: x = p0 + p1 + p2) and store them in MFMA FRAGMENT ORDER: a (32-row block, 16-wide k block, plane) fragment is
 //     1 KiB, lane l owning the 16 bytes of row (l & 31), k = 8 (l >> 5) .. + 7 -- exactly what v_mfma_f32_32x32x16_bf16 wants
 //     from lane l.  Both orientations are written (rows x channels for the forward / dX contraction over channels, channels x rows
 //     for the dW contraction over rows), so every GEMM of the stack is the same "NT" product of two plane sets.
@@ -28,8 +28,6 @@
 
 namespace papc {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
 enum { PG_EPI_STORE = 0, PG_EPI_FWD = 1, PG_EPI_FWD_GMAX = 2, PG_EPI_RED = 3 };
 enum { PG_PREP_PLAIN = 0, PG_PREP_CONCAT = 1, PG_PREP_BNRELU = 2, PG_PREP_DY_DENSE = 3, PG_PREP_DY_MAX = 4 };
 
@@ -41,12 +39,11 @@ __host__ __device__ static inline int64_t ru64(int64_t a, int64_t b) { return (a
 // of consecutive k.
 __device__ __forceinline__ void store_planes8(char *frag0, int slot, const float (&v)[8])
 {
-    uint2 a0, a1, a2, b0, b1, b2;
-    split3(make_float4(v[0], v[1], v[2], v[3]), a0, a1, a2);
-    split3(make_float4(v[4], v[5], v[6], v[7]), b0, b1, b2);
-    *reinterpret_cast<uint4 *>(frag0 + slot * 16) = make_uint4(a0.x, a0.y, b0.x, b0.y);
-    *reinterpret_cast<uint4 *>(frag0 + 1024 + slot * 16) = make_uint4(a1.x, a1.y, b1.x, b1.y);
-    *reinterpret_cast<uint4 *>(frag0 + 2048 + slot * 16) = make_uint4(a2.x, a2.y, b2.x, b2.y);
+    bf16x8 pl[3];
+    split8(v, pl);
+    *reinterpret_cast<uint4 *>(frag0 + slot * 16) = __builtin_bit_cast(uint4, pl[0]);
+    *reinterpret_cast<uint4 *>(frag0 + 1024 + slot * 16) = __builtin_bit_cast(uint4, pl[1]);
+    *reinterpret_cast<uint4 *>(frag0 + 2048 + slot * 16) = __builtin_bit_cast(uint4, pl[2]);
 }
 
 // ---- weights (any strided fp32 matrix) -> planes -----------------------------------------------------------------------------
@@ -464,8 +461,6 @@ __device__ __forceinline__ void pg_gemm_wg(const PgArgs &p, int t, const int nwg
             for (int ib = 0; ib < NB; ++ib)
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) bq[ib][pl] = *reinterpret_cast<const bf16x8 *>(sb + ((4 + wc * NB + ib) * 6 + kbl * 3 + pl) * 1024);
-            // a*b = a0b0 + (a0b1 + a1b0) + (a0b2 + a1b1 + a2b0), smallest terms first
-            constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
             if (p.dbg & 1) {   // keep the LDS reads alive without the matrix work
 #pragma unroll
                 for (int ia = 0; ia < 2; ++ia)
@@ -477,13 +472,14 @@ __device__ __forceinline__ void pg_gemm_wg(const PgArgs &p, int t, const int nwg
                     for (int pl = 0; pl < 3; ++pl) asm volatile("" ::"v"(bq[ib][pl]));
                 continue;
             }
+            // product t = BF16X3_PA[t] x BF16X3_PB[t] (smallest terms first); consecutive MFMAs go to different accumulators
 #pragma unroll
             for (int t = 0; t < 6; ++t)
 #pragma unroll
                 for (int ia = 0; ia < 2; ++ia)
 #pragma unroll
                     for (int ib = 0; ib < NB; ++ib)
-                        acc[ia][ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ia][PA[t]], bq[ib][PB[t]], acc[ia][ib], 0, 0, 0);
+                        acc[ia][ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ia][BF16X3_PA[t]], bq[ib][BF16X3_PB[t]], acc[ia][ib], 0, 0, 0);
         }
         buf = buf == NS - 1 ? 0 : buf + 1;
     }
