@@ -701,6 +701,29 @@ int papc_cloud_concat_conv_bwd_f32(const float *dz, const float *y, const float 
                                    int Cg, int Cout, float *dx, int64_t ldd, int accumulate, float *dw, float *dbias, float *dg, float *s_out,
                                    void *workspace, size_t workspace_bytes, papc_stream_t stream);
 
+/* One level of the KD-Net classifier (PAPC/models/classify/kdnet/kdnet.py:21-30): Conv1D(Cin, 3F, 1), ReLU, the kd-tree select, the max over
+ * adjacent point pairs -- computing only the selected third of the conv (csrc/kdconv.hip).  Point-major rows: x [B * dim, Cin] at x + m*ldx,
+ * out [B * dim / 2, F] contiguous, w [3F, Cin] (the Conv1D weight in place), bias [3F] (may be NULL), sel int32 split dims in 0..2 (values
+ * outside are clamped), cloud b's at sel + b*sel_stride (sel_stride = 0: one vector shared by every cloud).  For pre-pool row n of a cloud,
+ * s = sel[n]:   j = 3n + s,  k = j / dim,  p = j % dim:   y[n, f] = relu(bias[3f + k] + sum_c w[3f + k, c] x[p, c]),
+ * out[m, f] = max(y[2m, f], y[2m + 1, f])   (the source's index arithmetic).
+ *   papc_kdconv_ok       != 0 where the kernels take the shape: dim even and >= 2, Cin = 3 or a multiple of 32 up to 512, F a multiple of 32
+ *                        up to 512.  The calls below return PAPC_E_UNSUPPORTED elsewhere, naming the value.
+ *   papc_kdconv_fwd_f32  one launch: out, and win [B * dim / 2, F] bytes: which row of the pair won (0 = row 2m, also on an exact tie).
+ *   papc_kdconv_bwd_f32  from gout [B * dim / 2, F] and the forward's out and win (dy[n] = gout[n / 2] where row n won and out > 0):
+ *                        dx [B * dim, Cin] at dx + m*ldd (NULL: skipped; points that feed no row get exact zeros), dw [3F, Cin] and dbias [3F]
+ *                        (may be NULL), added to what they hold when accumulate != 0.  Per-chunk partial sums in the workspace
+ *                        (papc_kdconv_bwd_workspace bytes, 16-byte aligned), folded in chunk order: no atomics, bit-reproducible.
+ * B * dim <= 2^28; Cin >= 32: x / w / gout / out 16-byte aligned, ldx a multiple of 4.  Products: bf16x3 on v_mfma_f32_32x32x16_bf16 (fp32
+ * accuracy), Cin = 3: fmaf chains.  Timed under PAPC_K_MLP_GEMM / PAPC_K_BWD_DX / PAPC_K_BWD_DW. */
+int papc_kdconv_ok(int dim, int Cin, int F);
+int papc_kdconv_fwd_f32(const float *x, int64_t ldx, const int32_t *sel, int64_t sel_stride, const float *w, const float *bias, int B, int dim, int Cin,
+                        int F, float *out, uint8_t *win, papc_stream_t stream);
+size_t papc_kdconv_bwd_workspace(int B, int dim, int Cin, int F);
+int papc_kdconv_bwd_f32(const float *gout, const float *out, const uint8_t *win, const float *x, int64_t ldx, const int32_t *sel, int64_t sel_stride,
+                        const float *w, int B, int dim, int Cin, int F, float *dx, int64_t ldd, float *dw, float *dbias, int accumulate, void *workspace,
+                        size_t workspace_bytes, papc_stream_t stream);
+
 /* Axis-aligned bitmask NMS: nms_gpu of pointpillars/libs/ops/non_max_suppression/nms_gpu.py:130-164 (CUDA twin
  * libs/ops/cc/nms/nms_kernel.cu.cc:38-157), all on the device.  dets [N,5] = (x1, y1, x2, y2, score) fp32, N <= 65536.
  * keep [N] int32 receives the ORIGINAL indices of the kept boxes in descending-score order (ties: higher index first, the

@@ -113,6 +113,75 @@ def PNSegDataLoader(max_point=1024, batchsize=64, path='./data/', mode='train', 
     return PNSegDataGenerator
 
 
+def kd_split_dims(points, depth):
+    """tools/build_KDTree.py:6-53 (get_split_dims, build_ClasKDTree) for one cloud: points [n, 3] -> (split vectors, leaf order).
+
+    A balanced scipy cKDTree with one point per leaf is walked depth-first, lesser child first, down to ``depth`` levels below the root.  A
+    missing child stands in for by its parent (a leaf above the last level is followed as if it were its own children).  Every node above
+    the last level appends its split dim TWICE to its level's vector -- where it has none (a leaf, -1) the split dim of the node it was
+    reached from, or 0 if that has none either.  At the last level a node contributes one point index (drawn with np.random.choice, the
+    source's call, where a leaf holds several identical points).  Returns the vectors ordered deepest level first -- lengths 2^depth,
+    2^(depth-1), ... 2, int64, the order the source's dict of lists ends up in and KDNet consumes -- and the [2^depth] point indices in leaf
+    order (the source's tree[-1], its level-0 point order)."""
+    from scipy.spatial import cKDTree
+    root = cKDTree(points, leafsize=1, balanced_tree=True).tree
+    dims = [[] for _ in range(depth)]
+    order = []
+
+    def walk(node, level, parent):
+        if node is None:
+            node = parent
+        if level >= depth:
+            idx = node.indices
+            if len(idx) > 1:
+                idx = idx[np.random.choice(range(len(idx)), 1)]
+            order.append(int(idx[0]))
+            return
+        walk(node.lesser, level + 1, node)
+        walk(node.greater, level + 1, node)
+        d = node.split_dim
+        if d == -1:
+            d = parent.split_dim if parent.split_dim > -1 else 0
+        dims[level] += [d, d]
+
+    walk(root, 0, None)
+    return [np.asarray(v, dtype=np.int64) for v in reversed(dims)], np.asarray(order, dtype=np.int64)
+
+
+def KDClasDataLoader(max_point=1024, batchsize=64, path='./data/', mode='train', opener=None):
+    """kdloader.py:8-58.  The kd-tree of every cloud of the split is built once, at load time (tools/build_KDTree.py: kd_split_dims above); the
+    points are stored in the tree's leaf order.  Each call of the returned function = one epoch of
+    ``([points [b, 3, n] f32, split dims [b, 2n - 2] int32], label [b, 1] i64)`` with n = 2^levels, levels = log2(max_point) as the source
+    takes it: a cloud's ten (for 1024 points) split vectors packed in the order KDNet consumes them, lengths n, n/2, ... 2
+    (kdnet.pack_split_dims takes the batch as it comes).  The reference yields one cloud per step whatever ``batchsize`` says (kdloader.py:
+    52-56); ``batchsize=1`` reproduces it, a larger one stacks that many clouds.  scipy is imported on first use."""
+    levels = int((np.log(max_point) / np.log(2)).astype(int))                                      # kdloader.py:10
+    opener = opener or default_opener
+    points, splits, labels = [], [], []
+    for name in _files_of(mode):
+        f = opener(os.path.join(path, name))
+        data = np.asarray(f['data'])[:, :max_point, :]
+        for cloud in data:
+            dims, order = kd_split_dims(cloud, levels)                                             # kdloader.py:37-41
+            splits.append(np.concatenate(dims).astype(np.int32))
+            points.append(np.ascontiguousarray(cloud[order].T, dtype=np.float32))                  # tree[-1].transpose(0, 2, 1), :41, :54
+        labels.append(np.asarray(f['label']).astype(np.int64).reshape(len(data), -1))
+    n = 1 << levels
+    points = np.stack(points) if points else np.zeros((0, 3, n), np.float32)
+    splits = np.stack(splits) if splits else np.zeros((0, 2 * n - 2), np.int32)
+    labels = np.concatenate(labels, axis=0) if labels else np.zeros((0, 1), np.int64)
+    index_list = list(range(len(points)))
+
+    def KDClasDataGenerator():
+        if mode == 'train':
+            random.shuffle(index_list)                                                             # kdloader.py:49-50
+        for lo in range(0, len(index_list), batchsize):
+            sel = index_list[lo:lo + batchsize]
+            yield [points[sel], splits[sel]], labels[sel]
+
+    return KDClasDataGenerator
+
+
 _PN_MODELS = ('pointnet_basic', 'pointnet', 'vfe', 'pointnet2_ssg', 'pointnet2_msg')
 
 

@@ -6,6 +6,7 @@
   PointNet2_SSG_Seg / PointNet2_MSG_Seg    <- /root/reference/PAPC/models/segment/pointnet2/pointnet2.py:6-52, :54-100
   PointNet_Seg (T-Net PointNet)            <- /root/reference/PAPC/models/segment/pointnet/pointnet.py:4-114
   PointNet_Basic_Seg                       <- /root/reference/PAPC/models/segment/pointnet_base/pointnet_base.py:4-80
+  KDNet                                    <- PAPC/models/classify/kdnet/kdnet.py:5-49
 
 Inputs are ``[B,3,N]`` float32 (``[B,6,N]`` with normals).  Everything runs in libpapc_hip.so, in train AND eval mode, the FC heads included
 (head.py); the nn.Linear / BatchNorm1d / Dropout modules are the parameter holders.  CPU tensors raise PapcError (there is no CPU path); the
@@ -536,3 +537,48 @@ class PointNet2_MSG_Seg(_PartSegBase):
         l2 = self.sa2(l1[0], l1[1], s[1], sampled=plan[1])                                         # :87
         l3 = self.sa3(l2[0], l2[1])                                                                # :88
         return l1, l2, l3
+
+
+class KDNet(nn.Module):
+    """KD-Net classifier (PAPC/models/classify/kdnet/kdnet.py:5-49): ten levels of Conv1D(Cin, 3F, 1) + ReLU + kd-tree select + pair max
+    (1024 points -> 1), then Linear(128, num_classes).  Every level is one kdnet.kdconv node (csrc/kdconv.hip: only the selected third of the
+    conv is computed), the FC is linear.linear_rows.  Layer names and widths are the source's, so checkpoint.export_state / import_state
+    exchange .pdparams with it directly.
+
+    forward(inputs): inputs = [points, split_dims] as the source's loader yields them.  points [B, 3, 1024] (numpy or a device tensor);
+    split_dims the source's list of ten arrays -- each [dim_l] (one cloud, or shared by the batch) or [B, dim_l], dim_l = 1024, 512, ... 2 --
+    or one packed int32 tensor [2046] / [B, 2046] (kdnet.pack_split_dims; datasets.KDClasDataLoader yields the packed form).  -> [B, num_classes]"""
+
+    WIDTHS = ((3, 32), (32, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256), (256, 512), (512, 512), (512, 128))   # :8-17
+
+    def __init__(self, name_scope='KDNet_', num_classes=10):
+        super().__init__()
+        for i, (cin, f) in enumerate(self.WIDTHS):
+            setattr(self, "conv%d" % (i + 1), nn.Conv1d(cin, f * 3, 1, 1))
+        self.fc = nn.Linear(128, num_classes)                                                    # :18
+
+    def forward(self, inputs):
+        import numpy as np
+        from . import kdnet
+        from .copyops import contiguous_copy
+        from .linear import linear_rows
+        points, split_dims = inputs[0], inputs[1]
+        if isinstance(points, np.ndarray):                                                       # :31 paddle.to_tensor
+            dev = next(self.parameters()).device
+            if dev.type != "cuda":
+                raise _lib.PapcError("KDNet needs its parameters on a CUDA (ROCm) device: there is no CPU fallback")
+            points = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).to(dev)
+        x = torch.as_tensor(points).float()
+        if not x.is_cuda or next(self.parameters()).device != x.device:
+            raise _lib.PapcError("KDNet needs CUDA (ROCm) tensors and parameters on one device: there is no CPU fallback")
+        if x.dim() != 3 or x.shape[1] != 3:
+            raise _lib.PapcError("KDNet: points [B, 3, %d] expected, got %s" % (kdnet.DIMS[0], tuple(x.shape)))
+        B, _, N = x.shape
+        if N != kdnet.DIMS[0]:
+            raise _lib.PapcError("KDNet: the source's ten levels halve %d points down to one: N = %d points per cloud, %d expected"
+                                 % (kdnet.DIMS[0], N, kdnet.DIMS[0]))
+        sel = kdnet.pack_split_dims(split_dims, B, x.device)
+        rows = contiguous_copy(x.transpose(1, 2)).view(B * N, 3)                                 # the planar coordinates as point rows
+        for i, dim in enumerate(kdnet.DIMS):                                                     # :35-44
+            rows = kdnet.kdconv(rows, kdnet.level_split_dims(sel, i), getattr(self, "conv%d" % (i + 1)), B, dim)
+        return linear_rows(rows, self.fc.weight, self.fc.bias)                                   # :45-46 ([B, 128, 1] -> [B, 128])
