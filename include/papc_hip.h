@@ -601,7 +601,8 @@ int papc_points_to_voxel_f32(const float *points, int N, int ndim, const float *
 /* PointPillarsScatter.forward (pointpillars/models/bones/pillars.py:122-142): canvas [B, C, ny, nx] (zero-filled here),
  * canvas[b, :, y, x] = voxel_features[p, :] for coords[p] = (b, z, y, x); a repeated cell keeps the LAST pillar, like the
  * numpy assignment of select_change (libs/functional.py:35-38).  owner [B, ny, nx] int32 is written here (winning pillar
- * per cell, -1 = empty) and read by the backward. */
+ * per cell, -1 = empty) and read by the backward.  Rows whose (b, y, x) lies outside [0,B) x [0,ny) x [0,nx) are ignored
+ * (z is never read) and get a zero gradient.  P = 0 gives the zero canvas; voxel_features and coords may then be NULL. */
 int papc_pillar_scatter_f32(const float *voxel_features, const int32_t *coords, int P, int C, int batch_size, int ny,
                             int nx, float *canvas, int32_t *owner, papc_stream_t stream);
 /* grad_features[p, :] = grad_canvas[b, :, y, x] if pillar p owns its cell, else 0 */
@@ -727,7 +728,8 @@ int papc_kdconv_bwd_f32(const float *gout, const float *out, const uint8_t *win,
 /* Axis-aligned bitmask NMS: nms_gpu of pointpillars/libs/ops/non_max_suppression/nms_gpu.py:130-164 (CUDA twin
  * libs/ops/cc/nms/nms_kernel.cu.cc:38-157), all on the device.  dets [N,5] = (x1, y1, x2, y2, score) fp32, N <= 65536.
  * keep [N] int32 receives the ORIGINAL indices of the kept boxes in descending-score order (ties: higher index first, the
- * order of a stable argsort reversed), num_out [1] their count.  workspace: papc_nms_workspace(N) bytes. */
+ * order of a stable argsort reversed; scores +0.0 and -0.0 compare equal and tie), num_out [1] their count.
+ * workspace: papc_nms_workspace(N) bytes. */
 size_t papc_nms_workspace(int N);
 int papc_nms_f32(const float *dets, int N, float nms_overlap_thresh, int32_t *keep, int32_t *num_out, void *workspace,
                  size_t workspace_bytes, papc_stream_t stream);
@@ -735,7 +737,7 @@ int papc_nms_f32(const float *dets, int N, float nms_overlap_thresh, int32_t *ke
  * against the other's four half-planes (Sutherland-Hodgman, ordered vertex list in registers, fp64 distances / crossings / shoelace on
  * the source's fp32 corners :366-389) -- not by the source's candidate list + angular sort; results agree with it to rounding wherever
  * the source's strict edge tests are not ties (coincident edges, e.g. identical boxes at a general angle, are rounding noise there and
- * exact here).
+ * exact here).  A box of exactly zero area (a point, an axis-parallel segment) has no interior to clip against: its intersection is 0.
  * NOT OFFERED, deliberately: a `reference_quirks` mode for that coincident-edge case.  The source's value for two boxes that share an edge
  * line is whatever its fp32 candidate list / angular sort leaves after ties between strict `>` tests (:235-278, :323-339) -- anything between 0
  * and the true IoU for the SAME pair depending on the angle's last bit (oracle/reference_np.py::quad_inter reproduces it) -- so rotated NMS

@@ -14,9 +14,9 @@
 
 namespace papc {
 
-__device__ __forceinline__ uint32_t ordered_f32(float f)   // order-preserving float -> uint32
-{
-    const uint32_t u = __float_as_uint(f);
+__device__ __forceinline__ uint32_t ordered_f32(float f)   // order-preserving float -> uint32; -0.0 and +0.0 share one key (they
+{                                                          // compare equal, so a stable argsort leaves them in index order)
+    const uint32_t u = f == 0.f ? 0u : __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -137,7 +137,9 @@ __device__ __forceinline__ double quad_area2(const Quad &q)
 // below is a compile-time constant after unrolling (a slot is picked with selects), so the lists stay in registers.
 __device__ double quad_intersection_area(const Quad &A, const Quad &B)
 {
-    const double wind = quad_area2(B) < 0.0 ? -1.0 : 1.0;      // inside = left of every edge for counter-clockwise B, right for clockwise
+    const double b2 = quad_area2(B);
+    if (b2 == 0.0) return 0.0;                                 // B is a point or an axis-parallel segment: no interior (every distance below would be 0 = "inside")
+    const double wind = b2 < 0.0 ? -1.0 : 1.0;                 // inside = left of every edge for counter-clockwise B, right for clockwise
     double px[8], py[8];
     int n = 4;
 #pragma unroll

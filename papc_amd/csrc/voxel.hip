@@ -213,8 +213,8 @@ int papc_points_to_voxel_f32(const float *points, int N, int ndim, const float *
 int papc_pillar_scatter_f32(const float *voxel_features, const int32_t *coords, int P, int C, int batch_size, int ny, int nx,
                             float *canvas, int32_t *owner, papc_stream_t stream)
 {
-    PAPC_REQUIRE(voxel_features && coords && canvas && owner, PAPC_E_INVALID, "papc_pillar_scatter_f32: null pointer");
     PAPC_REQUIRE(P >= 0 && C >= 1 && batch_size >= 1 && ny >= 1 && nx >= 1, PAPC_E_INVALID, "papc_pillar_scatter_f32: bad sizes");
+    PAPC_REQUIRE((P == 0 || (voxel_features && coords)) && canvas && owner, PAPC_E_INVALID, "papc_pillar_scatter_f32: null pointer");   // no pillars: nothing is read
     hipStream_t st = as_stream(stream);
     ProfScope prof(PAPC_K_PFN, st);
     const size_t cells = (size_t)batch_size * ny * nx;

@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from oracle import reference_np as R
+from tests import detect_cases as D
 
 pytestmark = pytest.mark.gpu
 
@@ -188,3 +189,118 @@ def test_rotate_nms_edge_cases():
     far = np.array([[10 * i, 0, 2, 1, 0.3 * i, 0.1 * i] for i in range(1, 6)], np.float32)
     assert rotate_nms_gpu(far, 0.1) == [4, 3, 2, 1, 0]
     assert rotate_iou_gpu(np.zeros((0, 5), np.float32), np.zeros((3, 5), np.float32)).shape == (0, 3)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# edges (inputs: tests/detect_cases.py; their ability to fail is checked by tests/test_oracle.py::test_detect_case_tables)
+# ---------------------------------------------------------------------------------------------------------------------
+def _ints(xs):
+    return [int(i) for i in xs]
+
+
+def test_nms_signed_zero_scores_tie():
+    """+0.0 and -0.0 compare equal: to the oracle's stable argsort they are one tie (higher index first), so the score key must not tell
+    them apart.  The 130-box input keeps 34 boxes with the zeros tied and 35 with +0.0 ranked first."""
+    from papc_amd.nms import nms_gpu
+    assert nms_gpu(D.ZERO_PAIR, 0.5) == _ints(R.nms_gpu(D.ZERO_PAIR, 0.5)) == [1]
+    swapped = np.ascontiguousarray(D.ZERO_PAIR[::-1])
+    assert nms_gpu(swapped, 0.5) == _ints(R.nms_gpu(swapped, 0.5)) == [1]
+    dets = D.zero_score_dets()
+    assert nms_gpu(dets, D.ZERO_NMS_THR) == _ints(R.nms_gpu(dets, D.ZERO_NMS_THR))
+
+
+def test_nms_exact_threshold():
+    """IoU == thr exactly (0.5 in float32 under the "+1" convention) does not suppress; one float32 step below it does."""
+    from papc_amd.nms import nms_gpu
+    below = np.nextafter(np.float32(0.5), np.float32(0))
+    assert nms_gpu(D.EXACT_THR_PAIR, 0.5) == _ints(R.nms_gpu(D.EXACT_THR_PAIR, 0.5)) == [0, 1]
+    assert nms_gpu(D.EXACT_THR_PAIR, below) == _ints(R.nms_gpu(D.EXACT_THR_PAIR, below)) == [0]
+
+
+def test_rotate_nms_signed_zero_scores_tie():
+    from papc_amd.nms import rotate_nms_gpu
+    assert rotate_nms_gpu(D.ROTATED_ZERO_PAIR, 0.5) == [1]
+    assert rotate_nms_gpu(np.ascontiguousarray(D.ROTATED_ZERO_PAIR[::-1]), 0.5) == [1]
+
+
+def _corner_iou(ac, bc):
+    """the device's IoU of the corner quadrilaterals ac[i], bc[i] (no standup pre-test), pair by pair"""
+    from papc_amd.nms import rbbox_iou
+    n = len(ac)
+    got = rbbox_iou(np.ascontiguousarray(ac), np.ascontiguousarray(bc), standup_iou=np.ones((n, n), np.float32), standup_thresh=0.0)
+    return got[np.arange(n), np.arange(n)].astype(np.float64)
+
+
+def test_rbbox_iou_named_pairs_and_winding():
+    """Containment (at KITTI range), coincidence, shared edge / corner, crossings, large angles, on host float32 corners.  The kernel
+    works in fp64 on the given corners and rounds once to fp32 (6e-8); the float64 hull oracle is good to 4e-9 here: 1e-6 leaves an order
+    of magnitude and still catches a missing vertex or a wrong crossing.  Both argument orders, and every corner order (`wind`)."""
+    a, b = D.named_boxes()
+    ac, bc = D.corners_of(a), D.corners_of(b)
+    want = D.rbbox_iou_pairs(ac, bc)
+    got = _corner_iou(ac, bc)
+    swapped = _corner_iou(bc, ac)
+    for i, name in enumerate(D.NAMED):
+        print("%-18s want %.9f got %.9f swapped %.9f" % (name, want[i], got[i], swapped[i]))
+    assert np.abs(got - want).max() <= 1e-6 and np.abs(swapped - want).max() <= 1e-6
+    for name in D.TOUCHING:
+        assert got[D.NAMED.index(name)] < 1e-6 and swapped[D.NAMED.index(name)] < 1e-6
+    for ra, rb in ((ac[:, ::-1], bc), (ac, bc[:, ::-1]), (ac[:, ::-1], bc[:, ::-1])):
+        assert np.abs(_corner_iou(ra, rb) - got).max() <= 1e-6
+        assert np.abs(_corner_iou(rb, ra) - swapped).max() <= 1e-6
+
+
+def test_rotate_iou_named_pairs_near_origin():
+    """The five-vector path (corners formed on the device) on the named pairs near the origin, against the float64 hull."""
+    from papc_amd.nms import rotate_iou_gpu_eval
+    keep = [i for i, n in enumerate(D.NAMED) if n != "containment"]
+    names = [D.NAMED[i] for i in keep]
+    a, b = D.named_boxes()
+    a, b = a[keep], b[keep]
+    want = D.inter_pairs(a, b)
+    idx = np.arange(len(a))
+    got = rotate_iou_gpu_eval(a, b, 2)[idx, idx].astype(np.float64)
+    swapped = rotate_iou_gpu_eval(b, a, 2)[idx, idx].astype(np.float64)
+    for i, name in enumerate(names):
+        print("%-18s want %.9g got %.9g swapped %.9g" % (name, want[i], got[i], swapped[i]))
+    bar = 1e-5 * np.maximum(1.0, want)
+    assert (np.abs(got - want) <= bar).all() and (np.abs(swapped - want) <= bar).all()
+    for name in D.TOUCHING + ("thin_cross",):
+        assert got[names.index(name)] < 1e-5 and swapped[names.index(name)] < 1e-5
+    iou = rotate_iou_gpu_eval(a, b, -1)[idx, idx]
+    for name in D.COINCIDENT_AXIS_ALIGNED:
+        assert abs(float(iou[names.index(name)]) - 1.0) <= 2e-6
+
+
+def test_rotated_iou_kitti_range():
+    """Car-sized boxes 40-70 m out, where a float32 step of a corner is up to 7.6e-6 m.  Host corners: the 1e-6 bar of the named pairs.
+    Device corners: cosf / sinf may leave a corner one float32 step from numpy's, which moves a rectangle's edge by that step and the area
+    by at most perimeter x step (detect_cases.corner_step_bar)."""
+    from papc_amd.nms import rbbox_iou, rotate_iou_gpu_eval
+    b, q, bc, qc, iou, inter = D.kitti_reference()
+    b, q, bc, qc = b.copy(), q.copy(), bc.copy(), qc.copy()               # (the shared reference is read-only; torch wants writable arrays)
+    n, k = len(b), len(q)
+    got = rbbox_iou(bc, qc, standup_iou=np.ones((n, k), np.float32), standup_thresh=0.0).astype(np.float64)
+    got_t = rbbox_iou(qc, bc, standup_iou=np.ones((k, n), np.float32), standup_thresh=0.0).astype(np.float64)
+    r1 = max(np.abs(got - iou).max(), np.abs(got_t.T - iou).max()) / 1e-6
+    area = rotate_iou_gpu_eval(b, q, 2).astype(np.float64)
+    bar = D.corner_step_bar(b, q, inter)
+    r2 = (np.abs(area - inter) / bar).max()
+    print("KITTI-range rotated IoU: largest error / bar = %.3f (host corners, bar 1e-6), %.3f (device corners, bar %.2e .. %.2e)"
+          % (r1, r2, bar.min(), bar.max()))
+    assert r1 <= 1.0
+    assert r2 <= 1.0
+
+
+def test_rotated_zero_area_boxes():
+    from papc_amd.nms import rotate_iou_gpu_eval, rotate_nms_gpu
+    z, o = D.ZERO_AREA[None], D.ZERO_AREA_OTHER[None]
+    for crit in (2, -1):
+        assert float(rotate_iou_gpu_eval(z, o, crit)[0, 0]) == 0.0
+        assert float(rotate_iou_gpu_eval(o, z, crit)[0, 0]) == 0.0
+    v = rotate_iou_gpu_eval(D.ZERO_AREA_SET, D.ZERO_AREA_SET, -1)
+    assert v.shape == (3, 3) and not (v > 0).any()                               # 0 / 0: zero or NaN, never an overlap
+    assert rotate_nms_gpu(D.ZERO_AREA_NMS, 0.5) == _ints(R.rotate_nms_gpu(D.ZERO_AREA_NMS, 0.5)) == [0, 1, 2]
+    # a box shrunk to a point has no interior to clip against: the intersection is empty whichever box is the clipper
+    p, h = D.POINT_BOX[None], D.POINT_HOST[None]
+    assert float(rotate_iou_gpu_eval(p, h, 2)[0, 0]) == 0.0 and float(rotate_iou_gpu_eval(h, p, 2)[0, 0]) == 0.0

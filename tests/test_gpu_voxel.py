@@ -5,6 +5,7 @@ import torch
 
 from oracle import reference_np as R
 from papc_amd.voxel import PointPillarsScatter, points_to_voxel
+from tests import detect_cases as D
 
 pytestmark = pytest.mark.gpu
 
@@ -130,3 +131,106 @@ def test_frame_to_bev_pipeline(dev):
     assert int((bev.abs().sum(1) > 0).sum()) <= len(vox)
     bev.square().mean().backward()
     assert all(q.grad is not None and torch.isfinite(q.grad).all() for q in pfn.parameters())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# edges (inputs: tests/detect_cases.py; their ability to fail is checked by tests/test_oracle.py::test_detect_case_tables)
+# ---------------------------------------------------------------------------------------------------------------------
+def _assert_voxels_equal(got, want):
+    (v, c, m), (rv, rc, rn) = got, want
+    assert tuple(v.shape) == rv.shape and tuple(c.shape) == rc.shape and tuple(m.shape) == rn.shape
+    assert c.dtype == torch.int32 and m.dtype == torch.int32
+    assert np.array_equal(c.cpu().numpy(), rc)
+    assert np.array_equal(m.cpu().numpy(), rn)
+    assert np.array_equal(v.cpu().numpy(), rv)
+
+
+@pytest.mark.parametrize("max_voxels", D.GRID3_MAX_VOXELS)
+@pytest.mark.parametrize("reverse", [True, False])
+@pytest.mark.parametrize("ndim", D.GRID3_NDIMS)
+@pytest.mark.parametrize("grid", list(D.GRIDS3))
+def test_points_to_voxel_3d_grid(dev, grid, ndim, reverse, max_voxels):
+    """A grid several cells deep in z (c[2] != 0 in cell_of), point widths 3 / 4 / 6, both coordinate orders, with and without the
+    max_voxels cut.  grid8x10x8 has equal x and z sizes; grid8x10x6 has three different ones, so a cell index built with the wrong axis'
+    size merges or splits cells there."""
+    pts = D.grid3_points(ndim)
+    got = points_to_voxel(torch.from_numpy(pts).to(dev), **D.GRIDS3[grid], max_points=D.GRID3_MAX_POINTS, reverse_index=reverse,
+                          max_voxels=max_voxels)
+    _assert_voxels_equal(got, D.voxel_oracle(("grid3", grid, ndim, reverse, max_voxels)))
+
+
+def test_points_to_voxel_boundary_lattice(dev):
+    """Points on the KITTI grid's cell boundaries and one float32 step either side: floorf((p - lo) / vs) decides in float32 (a fast or
+    reciprocal divide would move points across cells), and the upper bound is outside."""
+    pts = D.lattice_points()
+    got = points_to_voxel(torch.from_numpy(pts).to(dev), **D.LATTICE_KW)
+    _assert_voxels_equal(got, D.voxel_oracle(("lattice",)))
+
+
+@pytest.mark.parametrize("name", ["same_point_300", "one_point", "max_voxels_1", "all_outside", "cut_at_last_point", "exactly_max_voxels"])
+def test_points_to_voxel_small_cases(dev, name):
+    pts, kw = D.voxel_small_cases()[name]
+    want = D.voxel_oracle(("small", name))
+    t = torch.from_numpy(pts).to(dev)
+    got = points_to_voxel(t, **kw)
+    _assert_voxels_equal(got, want)
+    if name == "same_point_300":
+        assert got[0][0, :, 3].cpu().numpy().tolist() == list(range(35))          # the first 35 in input order
+    if name == "max_voxels_1":
+        assert got[2].cpu().numpy().tolist() == [2]                                # the first cell's points after the break are dropped
+    if name == "all_outside":
+        assert tuple(got[0].shape) == (0, kw["max_points"], 4) and tuple(got[1].shape) == (0, 3) and tuple(got[2].shape) == (0,)
+    if name == "cut_at_last_point":
+        assert len(pts) == 21 and len(got[1]) == 10                               # the cut is at point N - 1
+    pv, pc, pn, cnt = points_to_voxel(t, **kw, padded=True)
+    m = len(want[1])
+    assert tuple(cnt.shape) == (1,) and int(cnt) == m
+    assert tuple(pv.shape) == (kw["max_voxels"], kw["max_points"], 4) and tuple(pc.shape) == (kw["max_voxels"], 3) and tuple(pn.shape) == (kw["max_voxels"],)
+    _assert_voxels_equal((pv[:m], pc[:m], pn[:m]), want)
+    assert not pv[m:].any() and not pc[m:].any() and not pn[m:].any()
+
+
+def test_points_to_voxel_back_to_back(dev):
+    """Two calls on one stream with no host read between them: flags, cut word and workspace of the first (cut in the middle of the frame)
+    do not leak into the second (no cut)."""
+    p1, p2 = _frame(4000, 7 + 4000), _frame(200, 7 + 200)
+    t1, t2 = torch.from_numpy(p1).to(dev), torch.from_numpy(p2).to(dev)
+    first = points_to_voxel(t1, **KITTI, max_points=100, reverse_index=True, max_voxels=150, padded=True)
+    second = points_to_voxel(t2, **KITTI, max_points=100, reverse_index=True, max_voxels=12000, padded=True)
+    rv, rc, rn = R.points_to_voxel(p2, **KITTI, max_points=100, reverse_index=True, max_voxels=12000)
+    m = int(second[3])
+    assert m == len(rc) and int(first[3]) == 150
+    _assert_voxels_equal((second[0][:m], second[1][:m], second[2][:m]), (rv, rc, rn))
+    assert not second[0][m:].any() and not second[2][m:].any()
+    w1 = R.points_to_voxel(p1, **KITTI, max_points=100, reverse_index=True, max_voxels=150)
+    _assert_voxels_equal((first[0], first[1], first[2]), w1)
+
+
+@pytest.mark.parametrize("P", D.SCATTER_P)
+@pytest.mark.parametrize("C", D.SCATTER_C)
+def test_pillar_scatter_edges(dev, C, P):
+    """Channel counts either side of one 64-lane pass, pillar counts that do not fill the last block of four, rows outside the canvas
+    (ignored, zero gradient), a cell shared by five pillars (the last one wins), non-zero z (never read).  Bit-exact both ways."""
+    B, ny, nx = D.SCATTER_DIMS["B"], D.SCATTER_DIMS["ny"], D.SCATTER_DIMS["nx"]
+    feats, coords, grad = D.scatter_case(P, C)
+    canvas, gref = D.scatter_expected(feats, coords, grad)
+    tf = torch.from_numpy(feats).to(dev).requires_grad_(True)
+    out = PointPillarsScatter([1, C, ny, nx], num_input_features=C)(tf, torch.from_numpy(coords).to(dev), B)
+    assert tuple(out.shape) == (B, C, ny, nx)
+    assert np.array_equal(out.detach().cpu().numpy(), canvas)
+    out.backward(torch.from_numpy(grad).to(dev))
+    got = tf.grad.cpu().numpy()
+    assert got.shape == gref.shape and np.array_equal(got, gref)
+    assert not got[~D.scatter_inside(coords)].any()
+
+
+@pytest.mark.parametrize("C", [1, 64])
+def test_pillar_scatter_empty(dev, C):
+    """No pillars (an empty batch): the zero canvas, and a [0, C] gradient through the autograd node."""
+    B, ny, nx = D.SCATTER_DIMS["B"], D.SCATTER_DIMS["ny"], D.SCATTER_DIMS["nx"]
+    tf = torch.zeros(0, C, device=dev, requires_grad=True)
+    out = PointPillarsScatter([1, C, ny, nx], num_input_features=C)(tf, torch.zeros(0, 4, device=dev, dtype=torch.int32), B)
+    assert tuple(out.shape) == (B, C, ny, nx) and out.dtype == torch.float32 and not out.any()
+    assert out.grad_fn is not None
+    out.backward(torch.ones_like(out))
+    assert tf.grad is not None and tuple(tf.grad.shape) == (0, C)

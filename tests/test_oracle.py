@@ -285,3 +285,105 @@ def test_rbbox_iou_oracle_known_answers():
         b2 = np.concatenate([rng.uniform(0, 6, 2), rng.uniform(0.5, 4, 2), rng.uniform(-3, 3, 1)]).astype(np.float32)
         c1, c2 = R.rbbox_to_corners(b1), R.rbbox_to_corners(b2)
         assert abs(R.convex_quad_inter_area(c1, c2) - R.quad_inter(c1.astype(np.float64), c2.astype(np.float64), np.float64)) < 1e-9 * 50
+
+
+def test_detect_case_tables():
+    """The inputs of the detection-op edge tests (tests/detect_cases.py) meet the conditions that make them able to fail."""
+    from tests import detect_cases as D
+    # --- voxeliser, 3-D grid.  The first grid is 8 x 10 x 8: its x and z sizes coincide, so it cannot tell a cell index formed with g[0]
+    # from one formed with g[2]; the second grid (z cut to 6 cells) has three different sizes and can.
+    assert D.grid_size(**D.GRID3).tolist() == [8, 10, 8]
+    g = D.grid_size(**D.GRID3_DISTINCT).tolist()
+    assert g == [8, 10, 6] and len(set(g)) == 3
+    for name, grid in D.GRIDS3.items():
+        pts = D.grid3_points(4)
+        assert pts.shape == (1500, 4) and np.array_equal(D.grid3_points(6)[:, :3], pts[:, :3]) and np.array_equal(D.grid3_points(3), pts[:, :3])
+        cells, ok = D.cells_f32(pts, **grid)
+        assert (~ok).mean() >= 0.10                                              # out-of-range points
+        occ, cnt = np.unique(cells[ok], axis=0, return_counts=True)
+        assert len(occ) > 97 and cnt.max() > D.GRID3_MAX_POINTS                  # the max_voxels = 97 cut and the max_points clip both bite
+        assert len(np.unique(cells[ok][:, 2])) == D.grid_size(**grid)[2] > 1     # every z layer is used
+        full = D.voxel_oracle(("grid3", name, 4, True, 20000))
+        cut = D.voxel_oracle(("grid3", name, 4, True, 97))
+        assert len(full[1]) == len(occ) and len(cut[1]) == 97 and cut[2].sum() < full[2].sum() and full[2].max() == D.GRID3_MAX_POINTS
+    # --- voxeliser, boundary lattice
+    pts = D.lattice_points()
+    assert 5500 <= len(pts) <= 7000
+    cr, vs = np.asarray(D.KITTI["coors_range"], np.float32), np.asarray(D.KITTI["voxel_size"], np.float32)
+    quo = (pts[:, :2] - cr[:2]) / vs[:2]
+    assert quo.dtype == np.float32
+    assert ((quo == np.floor(quo)).any(1)).mean() >= 0.25                        # the float32 quotient is an exact integer in x or y
+    top = pts[:, 0] == cr[3]                                                     # float32(432) * float32(0.16) is one step BELOW float32(69.12): its upper neighbour is the bound
+    assert top.sum() >= 30 and quo[top, 0].min() >= 432 and (pts[:, 1] >= cr[4]).sum() >= 30
+    top |= pts[:, 1] >= cr[4]
+    assert len(R.points_to_voxel(pts[top], **D.LATTICE_KW)[1]) == 0              # the oracle drops the points on the upper bound
+    lv, lc, ln = D.voxel_oracle(("lattice",))
+    assert len(lc) > 1000 and 2 <= ln.max() <= 5 and lc[:, 2].max() == 431 and lc[:, 1].max() == 495
+    # --- voxeliser, small cases
+    small = D.voxel_small_cases()
+    ora = {k: D.voxel_oracle(("small", k)) for k in small}
+    assert ora["same_point_300"][2].tolist() == [35] and ora["same_point_300"][0][0, :, 3].tolist() == list(range(35))
+    assert ora["one_point"][2].tolist() == [1]
+    assert ora["max_voxels_1"][2].tolist() == [2] and ora["max_voxels_1"][0][0, :2, 3].tolist() == [0, 1]   # points 3, 4, 5 of the first cell are dropped
+    assert [a.shape for a in ora["all_outside"]] == [(0, 5, 4), (0, 3), (0,)]
+    assert len(small["cut_at_last_point"][0]) == 21 and ora["cut_at_last_point"][2].tolist() == [2] * 10
+    assert len(small["exactly_max_voxels"][0]) == 20 and ora["exactly_max_voxels"][2].tolist() == [2] * 10
+    # --- scatter
+    B, ny, nx = D.SCATTER_DIMS["B"], D.SCATTER_DIMS["ny"], D.SCATTER_DIMS["nx"]
+    feats, coords, grad = D.scatter_case(501, 7)
+    ok = D.scatter_inside(coords)
+    assert 0.04 <= (~ok).mean() <= 0.06 and (coords[:, 1] != 0).all()
+    for col, val in D.scatter_outside_kinds(B, ny, nx):
+        assert ((coords[:, col] == val) & ~ok).any()
+    shared = (coords[:, [0, 2, 3]] == np.array(D.SCATTER_SHARED_CELL)).all(1)
+    assert shared.sum() == 5
+    canvas, gref = D.scatter_expected(feats, coords, grad)
+    b, y, x = D.SCATTER_SHARED_CELL
+    last = np.nonzero(shared)[0].max()
+    assert np.array_equal(canvas[b, :, y, x], feats[last]) and np.array_equal(gref[last], grad[b, :, y, x])
+    assert not gref[~ok].any() and not gref[np.nonzero(shared)[0][:-1]].any()
+    _, c3, _ = D.scatter_case(3, 7)
+    assert D.scatter_inside(c3).tolist() == [True, False, True] and (c3[0, [0, 2, 3]] == c3[2, [0, 2, 3]]).all()
+    assert D.scatter_inside(D.scatter_case(1, 7)[1]).all()
+    # --- axis-aligned NMS: signed zeros and the exact threshold
+    assert np.signbit(D.ZERO_PAIR[:, 4]).tolist() == [False, True]
+    assert [int(i) for i in R.nms_gpu(D.ZERO_PAIR, 0.5)] == [1] and [int(i) for i in R.nms_gpu(D.ZERO_PAIR[::-1], 0.5)] == [1]
+    dets = D.zero_score_dets()
+    assert dets.shape == (130, 5) and (dets[:, 4] == 0).all() and 30 < np.signbit(dets[:, 4]).sum() < 100
+    tie = [int(i) for i in R.nms_gpu(dets, D.ZERO_NMS_THR)]
+    split = [int(i) for i in R.nms_gpu(D.rank_positive_zero_first(dets), D.ZERO_NMS_THR)]
+    print("signed-zero NMS: %d kept with the zeros tied, %d kept with +0.0 ranked above -0.0" % (len(tie), len(split)))
+    assert tie != split and (len(tie), len(split)) == (34, 35)                   # the test can tell the two orders apart
+    assert R.nms_iou(D.EXACT_THR_PAIR[0], D.EXACT_THR_PAIR[1]) == np.float32(0.5)
+    assert [int(i) for i in R.nms_gpu(D.EXACT_THR_PAIR, 0.5)] == [0, 1]
+    assert [int(i) for i in R.nms_gpu(D.EXACT_THR_PAIR, np.nextafter(np.float32(0.5), np.float32(0)))] == [0]
+    # --- rotated IoU: named pairs
+    a, b = D.named_boxes()
+    inter = D.inter_pairs(a, b)
+    for i, name in enumerate(D.NAMED):
+        if name in D.KNOWN_AREAS:
+            assert abs(inter[i] - D.KNOWN_AREAS[name]) <= 2e-6, (name, inter[i])
+    ac, bc = D.corners_of(a), D.corners_of(b)
+    assert ac.dtype == np.float32
+    iou = D.rbbox_iou_pairs(ac, bc)
+    assert all(iou[D.NAMED.index(n)] < 1e-6 for n in D.TOUCHING) and all(abs(iou[D.NAMED.index(n)] - 1) < 1e-6 for n in D.COINCIDENT_AXIS_ALIGNED)
+    for ra, rb in ((ac[:, ::-1], bc), (ac, bc[:, ::-1]), (ac[:, ::-1], bc[:, ::-1])):    # the oracle does not depend on the corner order
+        assert np.abs(D.rbbox_iou_pairs(np.ascontiguousarray(ra), np.ascontiguousarray(rb)) - iou).max() <= 1e-9
+    # --- rotated IoU: KITTI range
+    kb, kq, kbc, kqc, kiou, kinter = D.kitti_reference()
+    assert kb.shape == kq.shape == (60, 5) and kb[:, 0].min() > 35 and np.abs(kbc).max() > 64
+    assert (kinter > 0.1).sum() >= 300
+    worst = 0.0
+    for boxes, c32 in ((kb, kbc), (kq, kqc)):
+        c64 = R.center_to_corner_box2d(boxes[:, :2].astype(np.float64), boxes[:, 2:4].astype(np.float64), boxes[:, 4].astype(np.float64))
+        step = np.spacing(np.abs(c64).max((1, 2)).astype(np.float32)).astype(np.float64)[:, None, None]   # of the box's largest coordinate, as in the bar
+        worst = max(worst, float((np.abs(c32 - c64) / step).max()))
+        r32 = np.stack([R.rbbox_to_corners(x) for x in boxes]).reshape(-1, 4, 2)
+        worst = max(worst, float((np.abs(r32 - c64) / step).max()))
+    print("KITTI-range host float32 corners: at most %.2f spacings from the float64 corners" % worst)
+    assert worst <= 1.0
+    bar = D.corner_step_bar(kb, kq, kinter)
+    assert bar.shape == (60, 60) and bar.max() < 1e-3
+    # --- zero-area boxes
+    assert [int(i) for i in R.rotate_nms_gpu(D.ZERO_AREA_NMS, 0.5)] == [0, 1, 2]
+    assert (D.ZERO_AREA_SET[:, 2] * D.ZERO_AREA_SET[:, 3] == 0).all() and D.ZERO_AREA[2] * D.ZERO_AREA[3] == 0
