@@ -963,7 +963,8 @@ int papc_pg_gemm_f32(const papc_pg_gemm *args, papc_stream_t stream);
 /* count (1 or 2) INDEPENDENT products in one launch, each computed exactly as papc_pg_gemm_f32 computes it (bit-identical results):
  * a layer's dX (PAPC_PG_RED or PAPC_PG_STORE) beside its split-K dW (PAPC_PG_STORE).  args is a HOST array.  Only the STORE and RED
  * epilogues, at most one RED: PAPC_E_UNSUPPORTED otherwise.  The launch is timed under the family of the product with more k stages per
- * workgroup.  Knob PAPC_PG_GROUP=0 (or a tile flavour forced by PAPC_PG_NB / PAPC_PG_NS) issues one papc_pg_gemm_f32 per product instead. */
+ * workgroup.  Knob PAPC_PG_GROUP=0 (or a tile flavour forced by PAPC_PG_NB / PAPC_PG_NS) issues one papc_pg_gemm_f32 per product instead.
+ * Knob PAPC_PG_PIPE=1 runs both entry points on the pipelined k16 ring instead of the k32 stage loop (bit-identical results; A/B). */
 int papc_pg_gemm_group_f32(const papc_pg_gemm *args, int count, papc_stream_t stream);
 
 /* Last forward layer of such a stack: stats [parts, 2, C] -> mean / invstd / scale / shift (+ running statistics), then

@@ -16,8 +16,9 @@
 //     from lane l.  Both orientations are written (rows x channels for the forward / dX contraction over channels, channels x rows
 //     for the dW contraction over rows), so every GEMM of the stack is the same "NT" product of two plane sets.
 //   * pg_gemm_kernel is then a pure matrix kernel: 1 KiB fragments go global -> LDS by LDS-DMA (global_load_lds_dwordx4, no VGPRs,
-//     no VALU), three k32 stages in a ring with a counted s_waitcnt vmcnt so two stages stay in flight across the single barrier
-//     of a stage, contiguous conflict-free ds_read_b128 of whole fragments, 48 (or 24) MFMAs per wave and stage.  Epilogues from
+//     no VALU) into a ring of two k32 stages (or, PAPC_PG_PIPE=1, of four k16 slots with a counted s_waitcnt vmcnt so two to
+//     three slots stay in flight across the single barrier of a k16 block: pg_ring_k16), contiguous conflict-free ds_read_b128 of
+//     whole fragments, 48 (or 24) MFMAs per wave and stage.  Epilogues from
 //     the accumulator layout: bias + store + BN statistics partials (+ the max / min / first-argmax over a 128-row group: the
 //     neighbourhood max of :219 when the group is one row tile), store + BN-backward sums of the layer below (dX), or split-K
 //     partial store (dW).
@@ -387,8 +388,121 @@ __device__ __forceinline__ void pg_epilogue(const PgArgs &p, floatx16 (&acc)[2][
 template <int NB>
 constexpr int pg_stage_bytes() { return (4 + 2 * NB) * 6 * 1024; }   // 32-row blocks of a stage (4 of A, then 2 NB of B) x 6 KiB: [2 k16][3 planes][1 KiB]
 
+// ---- the pipelined main loop (PAPC_PG_PIPE=1): the same LDS footprint as two k32 stages cut into FOUR k16 slots of (4 + 2 NB) x 3 KiB
+// ([32-row block][3 planes][1 KiB]; a k16 block of a row block is 3 contiguous KiB of the planes).  Per k16 block s:
+//     s_waitcnt vmcnt(this wave's loads of blocks s+2, s+3) lgkmcnt(0); s_barrier
+//         -> block s+1 has landed for every wave and every wave's LDS reads of slot s % 4 have returned
+//     LDS-DMA of block s+4 into slot s % 4
+//     ds_read_b128 of block s+1 into the OTHER fragment register set
+//     the 6 x 2 x NB MFMAs of block s from the set read one iteration earlier
+// so the LDS round trip passes under a block of matrix work, two to three blocks of DMA stay in flight across every barrier, and vmcnt
+// reaches 0 only at the last two blocks (nothing is in flight when the epilogue reuses the ring).  Every accumulator receives its k16
+// blocks in ascending order and, within a block, the six products in the order of BF16X3_PA / PB: bit-identical to the k32 loop.
+// Fragment loads per wave and slot are a compile-time function of the wave (the waits are counted): NB = 2: A row block w and B row
+// block w, 6; NB = 1: A row block w and, of B's 6 fragments, two each for waves 0 / 1 and one each for waves 2 / 3: 5, 5, 4, 4.
+template <int NB>
+constexpr int pg_slot_bytes() { return (4 + 2 * NB) * 3 * 1024; }
+
+template <int L>
+__device__ __forceinline__ void pg_wait_barrier_ahead(int ahead)   // ahead = younger blocks (of L loads each) that may stay in flight
+{
+    if (ahead >= 3) pg_wait_barrier<3 * L>();
+    else if (ahead == 2) pg_wait_barrier<2 * L>();
+    else if (ahead == 1) pg_wait_barrier<L>();
+    else pg_wait_barrier<0>();
+}
+
+template <int NB>
+__device__ __forceinline__ void pg_ring_k16(const PgArgs &p, floatx16 (&acc)[2][NB], char *smem, int lane, int w, int bi, int bj, int64_t st0, int nblk)
+{
+    constexpr int SLOT = pg_slot_bytes<NB>();
+    const int wr = w >> 1, wc = w & 1;
+    const unsigned lds0 = (unsigned)(uintptr_t)smem;
+    const int64_t kb0 = st0 * 2;
+    const char *ga = p.a + (((int64_t)bi * 4 + w) * p.KB + kb0) * 3072 + lane * 16;
+    const unsigned sa = (unsigned)(w * 3) * 1024;
+    // B: NB = 2: the three planes of row block w; NB = 1: fragments f0 .. of [2 row blocks][3 planes], f0 = 0, 2, 4, 5
+    const int f0 = NB == 2 ? 0 : (w < 2 ? 2 * w : 2 + w), f1 = f0 + 1;
+    const char *gb0, *gb1;
+    unsigned sbq;
+    if (NB == 2) {
+        gb0 = p.b + (((int64_t)bj * 4 + w) * p.KB + kb0) * 3072 + lane * 16;
+        gb1 = gb0;
+        sbq = (unsigned)((4 + w) * 3) * 1024;
+    } else {
+        gb0 = p.b + (((int64_t)bj * 2 + f0 / 3) * p.KB + kb0) * 3072 + (f0 % 3) * 1024 + lane * 16;
+        gb1 = p.b + (((int64_t)bj * 2 + f1 / 3) * p.KB + kb0) * 3072 + (f1 % 3) * 1024 + lane * 16;   // (waves 0 / 1 only)
+        sbq = (unsigned)(4 * 3 + f0) * 1024;
+    }
+    auto issue = [&](int s, int slot) {
+        const unsigned base = lds0 + (unsigned)slot * SLOT;
+        const int64_t o = (int64_t)s * 3072;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) glds16(ga + o + q * 1024, __builtin_amdgcn_readfirstlane(base + sa + q * 1024));
+        if (NB == 2) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) glds16(gb0 + o + q * 1024, __builtin_amdgcn_readfirstlane(base + sbq + q * 1024));
+        } else {
+            glds16(gb0 + o, __builtin_amdgcn_readfirstlane(base + sbq));
+            if (w < 2) glds16(gb1 + o, __builtin_amdgcn_readfirstlane(base + sbq + 1024));
+        }
+    };
+    auto wait = [&](int ahead) {
+        if (NB == 2) pg_wait_barrier_ahead<6>(ahead);
+        else if (w < 2) pg_wait_barrier_ahead<5>(ahead);
+        else pg_wait_barrier_ahead<4>(ahead);
+    };
+    bf16x8 af[2][2][3], bq[2][NB][3];   // two fragment sets: block s multiplies from set s & 1 while block s + 1 is read into the other
+    auto read = [&](bf16x8 (&a)[2][3], bf16x8 (&b)[NB][3], int slot) {
+        const char *sb = smem + slot * SLOT + lane * 16;
+#pragma unroll
+        for (int ia = 0; ia < 2; ++ia)
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) a[ia][pl] = *reinterpret_cast<const bf16x8 *>(sb + ((2 * wr + ia) * 3 + pl) * 1024);
+#pragma unroll
+        for (int ib = 0; ib < NB; ++ib)
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) b[ib][pl] = *reinterpret_cast<const bf16x8 *>(sb + ((4 + wc * NB + ib) * 3 + pl) * 1024);
+    };
+
+    const int n0 = nblk < 4 ? nblk : 4;
+    for (int s = 0; s < n0; ++s) issue(s, s);
+    wait(n0 - 1);                       // block 0 has landed for every wave
+    read(af[0], bq[0], 0);
+    for (int s2 = 0; s2 < nblk; s2 += 2) {   // nblk = 2 nst is even: two blocks per trip, so the fragment sets are compile-time
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int s = s2 + u;
+            const int left = nblk - 2 - s;
+            wait(left < 0 ? 0 : left > 2 ? 2 : left);
+            if (s + 4 < nblk) issue(s + 4, s & 3);
+            // (unconditional: after the last block this reads a stale or never-written slot that nobody writes any more, and nothing uses the result; a branch here
+            // would make the compiler's lgkmcnt before the MFMAs cover the reads just issued)
+            read(af[u ^ 1], bq[u ^ 1], (s + 1) & 3);
+            // product t = BF16X3_PA[t] x BF16X3_PB[t] (smallest terms first); consecutive MFMAs go to different accumulators
+#pragma unroll
+            for (int t = 0; t < 6; ++t)
+#pragma unroll
+                for (int ia = 0; ia < 2; ++ia)
+#pragma unroll
+                    for (int ib = 0; ib < NB; ++ib)
+                        acc[ia][ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[u][ia][BF16X3_PA[t]], bq[u][ib][BF16X3_PB[t]], acc[ia][ib], 0, 0, 0);
+            // issue order: one LDS read in the shadow of each of the first MFMAs (left alone the scheduler sinks the reads below the
+            // matrix work, straight in front of the next barrier's lgkmcnt(0))
+#pragma unroll
+            for (int i = 0; i < 6 + 3 * NB; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
+            }
+            __builtin_amdgcn_sched_group_barrier(0x008, 12 * NB - (6 + 3 * NB), 0);
+        }
+    }
+}
+
+
 // One workgroup of a product: workgroup t of the product's nwg, on the LDS ring smem (NS stages of pg_stage_bytes<NB>()).
-template <int EPI, int NB, int NS>
+// PIPE: the k16 ring above instead of the k32 stage loop (which alone reads the PAPC_PG_DBG bits).
+template <int EPI, int NB, int NS, bool PIPE>
 __device__ __forceinline__ void pg_gemm_wg(const PgArgs &p, int t, const int nwg, char *smem)
 {
     constexpr int STAGE = pg_stage_bytes<NB>();
@@ -438,6 +552,19 @@ __device__ __forceinline__ void pg_gemm_wg(const PgArgs &p, int t, const int nwg
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[ia][ib][r] = 0.f;
 
+    // ---- epilogue (full tiles take the straight-line flavour: a per-element predicate puts every store in its own basic block
+    // behind an s_waitcnt vmcnt(0))
+    auto epilogue = [&] {
+        const bool full = bi * 128 + 128 <= p.R1 && (bj + 1) * (NB * 64) <= p.R2;
+        if (full) pg_epilogue<EPI, NB, true>(p, acc, smem, lane, wr, wc, bi, bj, bz);
+        else pg_epilogue<EPI, NB, false>(p, acc, smem, lane, wr, wc, bi, bj, bz);
+    };
+    if constexpr (PIPE) {
+        pg_ring_k16<NB>(p, acc, smem, lane, w, bi, bj, st0, 2 * nst);
+        epilogue();
+        return;
+    }
+
     if (!(p.dbg & 2)) {
         issue(0, 0);
         if (NS == 3 && nst > 1) issue(1, 1);
@@ -484,34 +611,32 @@ __device__ __forceinline__ void pg_gemm_wg(const PgArgs &p, int t, const int nwg
         buf = buf == NS - 1 ? 0 : buf + 1;
     }
 
-    // ---- epilogue (full tiles take the straight-line flavour: a per-element predicate puts every store in its own basic block
-    // behind an s_waitcnt vmcnt(0))
     if (p.dbg & 8) return;
-    const bool full = bi * 128 + 128 <= p.R1 && (bj + 1) * (NB * 64) <= p.R2;
-    if (full) pg_epilogue<EPI, NB, true>(p, acc, smem, lane, wr, wc, bi, bj, bz);
-    else pg_epilogue<EPI, NB, false>(p, acc, smem, lane, wr, wc, bi, bj, bz);
+    epilogue();
 }
 
 // NS = stages in the LDS ring (NS - 1 of them in flight): 3 stages x 48 KiB is one workgroup per CU; (NB = 1, NS = 2) is 72 KiB, two
 // workgroups per CU whose waves fill each other's LDS-read and barrier gaps.
-template <int EPI, int NB, int NS>
+// PIPE (with NS = 2 only): the same bytes as four k16 slots.
+template <int EPI, int NB, int NS, bool PIPE>
 __global__ __launch_bounds__(256, 1) void pg_gemm_kernel(PgArgs p)
 {
+    static_assert(!PIPE || (NS == 2 && 4 * pg_slot_bytes<NB>() == NS * pg_stage_bytes<NB>()), "the k16 ring lives in the two-stage footprint");
     __shared__ __attribute__((aligned(1024))) char smem[NS * pg_stage_bytes<NB>()];
-    pg_gemm_wg<EPI, NB, NS>(p, blockIdx.x, gridDim.x, smem);
+    pg_gemm_wg<EPI, NB, NS, PIPE>(p, blockIdx.x, gridDim.x, smem);
 }
 
 // Two independent products in one grid (a layer's dX and its split-K dW): workgroups [0, n0) run product 0, the rest product 1, each
 // with its own tile numbering and epilogue and the arithmetic of its own launch.  One (NB = 1, NS = 2) ring of 72 KiB for both, so
 // two workgroups share a CU whichever products they belong to, and the second product's workgroups fill the CUs the first leaves
 // idle -- without the graph edge a parallel branch costs.
-template <int EPI0, int EPI1>
+template <int EPI0, int EPI1, bool PIPE>
 __global__ __launch_bounds__(256, 1) void pg_gemm_group_kernel(PgArgs p0, PgArgs p1, int n0)
 {
     __shared__ __attribute__((aligned(1024))) char smem[2 * pg_stage_bytes<1>()];
     const int t = blockIdx.x;
-    if (t < n0) pg_gemm_wg<EPI0, 1, 2>(p0, t, n0, smem);
-    else pg_gemm_wg<EPI1, 1, 2>(p1, t - n0, (int)gridDim.x - n0, smem);
+    if (t < n0) pg_gemm_wg<EPI0, 1, 2, PIPE>(p0, t, n0, smem);
+    else pg_gemm_wg<EPI1, 1, 2, PIPE>(p1, t - n0, (int)gridDim.x - n0, smem);
 }
 
 // ---- last forward layer: batch statistics -> BN constants, then BN + ReLU on the selected extreme of every (group, channel) ------
@@ -755,14 +880,19 @@ int papc_pg_gemm_f32(const papc_pg_gemm *g, papc_stream_t stream)
     if (nb == 0) nb = (g->R2 > 64 && t1 * cdiv(g->R2, 128) * split >= 200) ? 2 : 1;
     if (g->R2 <= 64) nb = 1;
     if (ns == 0) ns = 2;   // (96 / 72 KiB: the workgroup also fits beside a 49 KiB farthest-point-sampling workgroup of the sampling branch)
+    // PAPC_PG_PIPE=1 (the default; measured in DESIGN 3.8): the two-stage footprint as a four-slot k16 ring with the LDS-DMA in flight across the barriers
+    // (pg_ring_k16); 0, any PAPC_PG_DBG bit or PAPC_PG_NS=3: the k32 stage loop.  Bit-identical results either way.
+    const bool pipe = knob(KNOB_PG_PIPE) && ns == 2 && !p.dbg;
     p.g1 = (int)t1; p.g2 = (int)cdiv(g->R2, nb == 2 ? 128 : 64);
     const dim3 grid((unsigned)(p.g1 * p.g2 * split));
 #define PG_GO(E)                                                                                      \
     do {                                                                                              \
-        if (nb == 2 && ns == 3) hipLaunchKernelGGL((pg_gemm_kernel<E, 2, 3>), grid, dim3(256), 0, st, p);      \
-        else if (nb == 2) hipLaunchKernelGGL((pg_gemm_kernel<E, 2, 2>), grid, dim3(256), 0, st, p);            \
-        else if (ns == 3) hipLaunchKernelGGL((pg_gemm_kernel<E, 1, 3>), grid, dim3(256), 0, st, p);            \
-        else hipLaunchKernelGGL((pg_gemm_kernel<E, 1, 2>), grid, dim3(256), 0, st, p);                         \
+        if (nb == 2 && ns == 3) hipLaunchKernelGGL((pg_gemm_kernel<E, 2, 3, false>), grid, dim3(256), 0, st, p);      \
+        else if (nb == 2 && pipe) hipLaunchKernelGGL((pg_gemm_kernel<E, 2, 2, true>), grid, dim3(256), 0, st, p);     \
+        else if (nb == 2) hipLaunchKernelGGL((pg_gemm_kernel<E, 2, 2, false>), grid, dim3(256), 0, st, p);            \
+        else if (ns == 3) hipLaunchKernelGGL((pg_gemm_kernel<E, 1, 3, false>), grid, dim3(256), 0, st, p);            \
+        else if (pipe) hipLaunchKernelGGL((pg_gemm_kernel<E, 1, 2, true>), grid, dim3(256), 0, st, p);                \
+        else hipLaunchKernelGGL((pg_gemm_kernel<E, 1, 2, false>), grid, dim3(256), 0, st, p);                         \
     } while (0)
     switch (epi) {
     case PG_EPI_STORE: PG_GO(PG_EPI_STORE); break;
@@ -806,9 +936,16 @@ int papc_pg_gemm_group_f32(const papc_pg_gemm *g, int count, papc_stream_t strea
     hipStream_t st = as_stream(stream);
     ProfScope prof(g[f].family >= 0 && g[f].family < PAPC_K_COUNT ? g[f].family : PAPC_K_MISC, st);
     const dim3 grid((unsigned)(n[0] + n[1]));
-    if (e0 == PG_EPI_RED) hipLaunchKernelGGL((pg_gemm_group_kernel<PG_EPI_RED, PG_EPI_STORE>), grid, dim3(256), 0, st, p[f], p[s], n[f]);
-    else if (e1 == PG_EPI_RED) hipLaunchKernelGGL((pg_gemm_group_kernel<PG_EPI_STORE, PG_EPI_RED>), grid, dim3(256), 0, st, p[f], p[s], n[f]);
-    else hipLaunchKernelGGL((pg_gemm_group_kernel<PG_EPI_STORE, PG_EPI_STORE>), grid, dim3(256), 0, st, p[f], p[s], n[f]);
+#define PG_GO(E0, E1)                                                                                                              \
+    do {                                                                                                                           \
+        if (pipe) hipLaunchKernelGGL((pg_gemm_group_kernel<E0, E1, true>), grid, dim3(256), 0, st, p[f], p[s], n[f]);              \
+        else hipLaunchKernelGGL((pg_gemm_group_kernel<E0, E1, false>), grid, dim3(256), 0, st, p[f], p[s], n[f]);                  \
+    } while (0)
+    const bool pipe = knob(KNOB_PG_PIPE) && !knob(KNOB_PG_DBG);   // (PAPC_PG_NS=3 went the other way above)
+    if (e0 == PG_EPI_RED) PG_GO(PG_EPI_RED, PG_EPI_STORE);
+    else if (e1 == PG_EPI_RED) PG_GO(PG_EPI_STORE, PG_EPI_RED);
+    else PG_GO(PG_EPI_STORE, PG_EPI_STORE);
+#undef PG_GO
     return check_launch("papc_pg_gemm_group_f32");
 }
 
