@@ -39,6 +39,12 @@ class BwdDy(ctypes.Structure):
                 ("mean", c_p), ("invstd", c_p), ("scale", c_p), ("shift", c_p), ("c1", c_p), ("c2", c_p),
                 ("wrow", c_p), ("seg_grp", c_p), ("rows_dev", c_p), ("psel", c_p)]
 
+    def set_bn(self, y, cst, c12):
+        """the layer's output ``y`` (or None), its [4, C] constants block (mean, invstd, scale, shift) and c1 / c2 of a [2, C] tensor"""
+        self.y = ptr(y)
+        self.mean, self.invstd, self.scale, self.shift = cst_ptrs(cst)
+        self.c1, self.c2 = c12.data_ptr(), c12.data_ptr() + 4 * c12.stride(0)
+
 
 class GroupMax(ctypes.Structure):
     """papc_group_max"""
@@ -250,6 +256,12 @@ def stream_ptr():
 
 def ptr(t):
     return 0 if t is None else t.data_ptr()
+
+
+def cst_ptrs(cst):
+    """(mean, invstd, scale, shift): the rows of a layer's [4, C] BatchNorm constants block, as pointers"""
+    p, ld = cst.data_ptr(), 4 * cst.stride(0)
+    return p, p + ld, p + 2 * ld, p + 3 * ld
 
 
 def zeros(shape, device):

@@ -9,20 +9,15 @@ the result is a fresh contiguous tensor; the backward hands every input a contig
 import torch
 
 from . import _lib
-from ._lib import CopyJob, check, stream_ptr
+from ._lib import CopyJob
+from .nodeparts import launch_batched
 
 
 def _launch(jobs):
-    lib = _lib.load()
-    for k0 in range(0, len(jobs), 8):
-        chunk = jobs[k0:k0 + 8]
-        arr = (CopyJob * len(chunk))()
-        for a, (src, soff, sst, dst, doff, dst_st, B, R, C) in zip(arr, chunk):
-            a.src, a.dst = src.data_ptr() + 4 * soff, dst.data_ptr() + 4 * doff
-            a.B, a.R, a.C = B, R, C
-            a.sb, a.sr, a.sc = sst
-            a.db, a.dr, a.dc = dst_st
-        check(lib.papc_copy_strided_batch_f32(arr, len(chunk), stream_ptr()), "papc_copy_strided_batch_f32")
+    """jobs: (source, offset in floats, its strides, destination, offset, its strides, B, R, C)"""
+    launch_batched(CopyJob, [(src.data_ptr() + 4 * soff, dst.data_ptr() + 4 * doff, B, R, C, *sst, *dst_st)
+                             for src, soff, sst, dst, doff, dst_st, B, R, C in jobs],
+                   _lib.load().papc_copy_strided_batch_f32, "papc_copy_strided_batch_f32")
 
 
 class _CatCopy(torch.autograd.Function):

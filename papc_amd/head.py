@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
-from .mlp import grad_targets_of
+from .nodeparts import all_or_none, grad_targets_of
 
 MAX_ROWS = 256
 # PAPC_HEAD_CHAIN=1: the layers of a head as phases of ONE launch each way (papc_head_chain_fwd_f32 / _bwd_f32, grid barrier between the
@@ -194,15 +194,9 @@ class _Head(torch.autograd.Function):
         B = x0.shape[0]
         dev = x0.device
         st = stream_ptr()
-        tg = spec.grad_targets
-        if tg is not None and any(t is None for t in tg):    # (all of the head's parameters or none: a partial set goes through autograd)
-            tg = None
-        acc = 1 if tg is not None else 0
-        if tg is None:
-            shapes = [w1.shape, (w1.shape[0],), (w1.shape[0],), (w1.shape[0],), w2.shape, (w2.shape[0],), (w2.shape[0],),
-                      (w2.shape[0],), w3.shape, (w3.shape[0],)]
-            tg = [torch.empty(s, device=dev, dtype=torch.float32) for s in shapes]
-        dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2, dw3, db3 = tg
+        # (all of the head's parameters or none: a partial set goes through autograd)
+        shapes = [w1.shape] + [(w1.shape[0],)] * 3 + [w2.shape] + [(w2.shape[0],)] * 3 + [w3.shape, (w3.shape[0],)]
+        (dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2, dw3, db3), acc, grads = all_or_none(spec.grad_targets, shapes, dev)
         c1, c0 = w1.shape
         c2 = w2.shape[0]
         c3 = w3.shape[0]
@@ -230,7 +224,6 @@ class _Head(torch.autograd.Function):
                     ptr(dy1), ptr(dw1), ptr(db1), ptr(dg1), ptr(dbe1), acc, st), "papc_head_bwd_f32")
             if need_dx:
                 check(f(ptr(dy1), ptr(w1), c1, 0, 0, 0, 0, 0, 0.0, 0, 0, B, 0, c0, ptr(dx0), 0, 0, 0, 0, 0, st), "papc_head_bwd_f32")
-        grads = (None,) * 10 if acc else tuple(tg)
         return (None, None, None, None, dx0) + grads
 
 
@@ -309,13 +302,8 @@ class _HeadPlain(torch.autograd.Function):
         spec, p = ctx.spec, ctx.p
         B, dev, st = x0.shape[0], x0.device, stream_ptr()
         glogits = glogits.contiguous().float()
-        tg = spec.grad_targets
-        if tg is not None and any(t is None for t in tg):
-            tg = None
-        acc = 1 if tg is not None else 0
-        if tg is None:
-            tg = [torch.empty(s_, device=dev, dtype=torch.float32) for s_ in (w1.shape, (w1.shape[0],), w2.shape, (w2.shape[0],), w3.shape, (w3.shape[0],))]
-        dw1, db1, dw2, db2, dw3, db3 = tg
+        shapes = [w1.shape, (w1.shape[0],), w2.shape, (w2.shape[0],), w3.shape, (w3.shape[0],)]
+        (dw1, db1, dw2, db2, dw3, db3), acc, grads = all_or_none(spec.grad_targets, shapes, dev)
         c1, c0 = w1.shape
         c2, c3 = w2.shape[0], w3.shape[0]
         dy2 = torch.empty(B, c2, device=dev, dtype=torch.float32)
@@ -338,7 +326,6 @@ class _HeadPlain(torch.autograd.Function):
                   "papc_head_bwd_f32")
             if need_dx:
                 check(f(ptr(dy1), ptr(w1), c1, 0, 0, 0, 0, 0, 0.0, 0, 0, B, 0, c0, ptr(dx0), 0, 0, 0, 0, 0, st), "papc_head_bwd_f32")
-        grads = (None,) * 6 if acc else tuple(tg)
         return (None, None, dx0) + grads
 
 

@@ -21,6 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
+from .nodeparts import all_or_none, grad_targets_of
 
 _KDCONV = os.environ.get("PAPC_KDCONV", "1") != "0"          # A/B switch: 0 = the source's op sequence in torch device ops
 DIMS = (1024, 512, 256, 128, 64, 32, 16, 8, 4, 2)            # points per cloud entering level 1 .. 10 (kdnet.py:35-44)
@@ -59,18 +60,14 @@ class _KDConv(torch.autograd.Function):
         lib = _lib.load()
         dev = rows.device
         gout = gout.contiguous().float()
-        tg = ctx.targets
-        inplace = tg is not None and tg[0] is not None and (not ctx.has_bias or tg[1] is not None)
-        dw = tg[0].view(3 * f, cin) if inplace else torch.empty(3 * f, cin, device=dev, dtype=torch.float32)
-        db = None
-        if ctx.has_bias:
-            db = tg[1] if inplace else torch.empty(3 * f, device=dev, dtype=torch.float32)
+        tg, acc, grads = all_or_none(ctx.targets, [(3 * f, cin)] + ([(3 * f,)] if ctx.has_bias else []), dev)
+        dw, db = tg[0], (tg[1] if ctx.has_bias else None)
         dx = torch.empty(B * dim, cin, device=dev, dtype=torch.float32) if ctx.needs_input_grad[1] else None
         nbytes = lib.papc_kdconv_bwd_workspace(B, dim, cin, f)
         ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
         check(lib.papc_kdconv_bwd_f32(ptr(gout), ptr(out), ptr(win), ptr(rows), rows.stride(0), ptr(sel), ss, ptr(w), B, dim, cin, f, ptr(dx), cin,
-                                      ptr(dw), ptr(db), 1 if inplace else 0, ptr(ws), nbytes, stream_ptr()), "papc_kdconv_bwd_f32")
-        return None, dx, None, (None if inplace else dw), (None if inplace else db), None, None
+                                      ptr(dw), ptr(db), acc, ptr(ws), nbytes, stream_ptr()), "papc_kdconv_bwd_f32")
+        return (None, dx, None) + grads + (None,) * (4 - len(grads))
 
 
 def _kdconv_torch(rows, sel, conv, B, dim):
@@ -108,7 +105,6 @@ def kdconv(rows, sel, conv, B, dim):
                              % (B * dim, cin, dim, B, dim, tuple(rows.shape), tuple(sel.shape), cout))
     if not (_KDCONV and kernel_ok(dim, cin, cout // 3)):
         return _kdconv_torch(rows, sel, conv, B, dim)
-    from .mlp import grad_targets_of
     if not (rows.stride(1) == 1 and (cin == 3 or (rows.stride(0) % 4 == 0 and rows.data_ptr() % 16 == 0))):
         rows = rows.contiguous()
     tg = grad_targets_of([conv.weight] + ([conv.bias] if conv.bias is not None else [])) if torch.is_grad_enabled() else None

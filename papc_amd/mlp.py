@@ -14,7 +14,9 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import BwdDy, BwdRed, GroupMax, GroupSrc, ReduceJob, ScatterDst, check, ptr, stream_ptr
+from ._lib import BwdDy, BwdRed, GroupMax, GroupSrc, ReduceJob, ScatterDst, check, cst_ptrs, ptr, stream_ptr
+from .nodeparts import DwPartials, LayerSlots, bn_bwd_sums, identity_bn, launch_batched
+from .nodeparts import grad_targets_of, _dw_rows_per_chunk      # noqa: F401  (re-exported: tests and tools import them from here)
 
 A_PLAIN, A_BNRELU, A_GROUP, A_XYZ = 0, 1, 2, 6
 DZ_DENSE, DZ_MAX = 0, 1
@@ -63,26 +65,12 @@ def _group_src(spec, xyz, new_xyz, feats, idx):
 import os
 _FUSE_RED = os.environ.get("PAPC_NO_RED") != "1"            # A/B switch for the BN-backward reduce fused into the dX epilogue
 _FUSE_GMAX = os.environ.get("PAPC_NO_GMAX") != "1"          # A/B switch for the fused neighbourhood-max epilogue
-_RESIDENT_WGS = int(os.environ.get("PAPC_PARTS", "512"))   # persistent-grid size (tuning knob shared with the C side)
 _LIN_GATHER = os.environ.get("PAPC_LIN_GATHER", "1") == "1"    # first grouped layer: linear map per source point, then gather-add (lingather.hip)
 _NOSTORE = os.environ.get("PAPC_NOSTORE", "1") == "1"   # the max-pooled last layer without its [M, C] output where the library has all three flavours (papc_mlp_max_nostore_ok)
 _SPARSE_MAX = os.environ.get("PAPC_SPARSE_MAX", "0") == "1"   # dX of the max-pooled last layer without reading its output y (papc_mlp_bwd_dx_max_f32)
-_DW_WGS = int(os.environ.get("PAPC_DW_WGS", "512"))         # workgroups of one dW launch (row chunks x output tiles)
 _PY_ORCH = os.environ.get("PAPC_PY_ORCH", "0") == "1"      # this module's own launch sequence instead of the library's papc_sa_mlp_fwd / _bwd (stack.py)
 _XYZ1 = os.environ.get("PAPC_XYZ1", "1") == "1"             # coordinates-only first layer through its input moments, never materialised (xyz1.hip)
 _XYZ_FUSE = os.environ.get("PAPC_XYZ_FUSE", "1") == "1"   # A/B switch (library orchestration only): 0 = the dX above a coordinates-only first layer is stored and read back by papc_xyz_l1_bwd_f32
-
-
-def _dw_rows_per_chunk(M, cout, cin, min_rows=256):
-    """Row-chunk size for the dW kernel: ONE residency wave of workgroups (256 CUs x 2 per CU = 512) in total, so
-    no tail round; chunks of >= 256 rows -- >= 64 for the gather-add layer's dW_f over the B N source points (sa_mlp.hip::dw_rows_per_chunk:
-    the same rule, bit for bit the same partial sums)."""
-    wide = 128 < cin <= 160
-    tiles = ((cout + 127) // 128) * (1 if wide else (cin + 127) // 128)
-    want = max(1, _DW_WGS // tiles)
-    rpc = (M + want - 1) // want
-    rpc = max(min_rows, ((rpc + 63) // 64) * 64)
-    return rpc
 
 
 # ---- W^T operands of the dX GEMMs, precomputed for several stacks in one launch -------------------------------------------------
@@ -236,8 +224,7 @@ class SharedMLPMax(torch.autograd.Function):
                 gram = torch.empty(16, device=dev, dtype=torch.float64)
                 rm, rv = (bn_buffers[l] if bn_buffers is not None else (None, None))
                 check(lib.papc_xyz_l1_finalize_f32(ptr(gpart), nparts, M, ptr(w2), cin, 0, ptr(b), ptr(gamma), ptr(beta), spec.eps, spec.momentum,
-                                                   cout, cst[0].data_ptr(), cst[1].data_ptr(), cst[2].data_ptr(), cst[3].data_ptr(), ptr(rm), ptr(rv),
-                                                   ptr(wf), ptr(gram), st), "papc_xyz_l1_finalize_f32")
+                                                   cout, *cst_ptrs(cst), ptr(rm), ptr(rv), ptr(wf), ptr(gram), st), "papc_xyz_l1_finalize_f32")
                 ys.append(None)
                 consts.append(cst)
                 prev_y, prev_sc, prev_sh = None, cst[2], cst[3]
@@ -279,11 +266,9 @@ class SharedMLPMax(torch.autograd.Function):
             cst = torch.empty(4, cout, device=dev, dtype=torch.float32)  # mean, invstd, scale, shift
             rm, rv = (bn_buffers[l] if bn_buffers is not None else (None, None))
             if ev:
-                check(lib.papc_bn_eval_consts_f32(ptr(rm), ptr(rv), ptr(gamma), ptr(beta), spec.eps, cout, cst[0].data_ptr(),
-                                                  cst[1].data_ptr(), cst[2].data_ptr(), cst[3].data_ptr(), st), "papc_bn_eval_consts_f32")
+                check(lib.papc_bn_eval_consts_f32(ptr(rm), ptr(rv), ptr(gamma), ptr(beta), spec.eps, cout, *cst_ptrs(cst), st), "papc_bn_eval_consts_f32")
             else:
-                check(lib.papc_bn_finalize_f32(ptr(stats), parts_l, M, cout, ptr(gamma), ptr(beta), spec.eps, spec.momentum,
-                                               cst[0].data_ptr(), cst[1].data_ptr(), cst[2].data_ptr(), cst[3].data_ptr(),
+                check(lib.papc_bn_finalize_f32(ptr(stats), parts_l, M, cout, ptr(gamma), ptr(beta), spec.eps, spec.momentum, *cst_ptrs(cst),
                                                ptr(rm), ptr(rv), st), "papc_bn_finalize_f32")
             ys.append(y)
             consts.append(cst)
@@ -349,9 +334,8 @@ class SharedMLPMax(torch.autograd.Function):
         cp = ctx.compact
         if cp is not None:
             grp.cidx, grp.seg_grp, grp.rows_dev = cp.cidx.data_ptr(), cp.seg_grp.data_ptr(), cp.rows.data_ptr()
-        n_parts = min(_RESIDENT_WGS, (M + 127) // 128)
         grads = [None] * (4 * L)
-        reduce_jobs = []   # (partial tensor, n_chunks, ld, n1, out1 ptr, n2, out2 ptr, accumulate): see the dW section
+        reduce_jobs = []   # (DwPartials, (dW pointer, db pointer, accumulate)): see the dW section
         grad_feats = None
         grad_x = None
         dz = None
@@ -394,15 +378,8 @@ class SharedMLPMax(torch.autograd.Function):
             cin = ctx.cin0 if l == 0 else params[4 * (l - 1)].shape[0]
             cst = consts[l]
             c12 = torch.empty(2, cout, device=dev, dtype=torch.float32)
-            tgt = spec.grad_targets[4 * l: 4 * l + 4] if spec.grad_targets is not None else None
-            inplace = tgt is not None and all(t is not None for t in tgt)
-            # the norm's two vectors can go in place on their own (a layer whose conv weight is a padded view keeps them off autograd)
-            gb_inplace = tgt is not None and tgt[2] is not None and tgt[3] is not None and not spec.eval_bn
-            if gb_inplace:   # accumulate straight into the parameters' .grad (flat-bucket views): no autograd add kernels
-                dgamma_p, dbeta_p = tgt[2].data_ptr(), tgt[3].data_ptr()
-            else:
-                dgb = torch.empty(2, cout, device=dev, dtype=torch.float32)  # dgamma, dbeta
-                dgamma_p, dbeta_p = dgb[0].data_ptr(), dgb[1].data_ptr()
+            s = LayerSlots(spec.grad_targets, l, w, spec.eval_bn, xyz_first_layer=(l == 0 and xyz1))
+            grads[4 * l: 4 * l + 4] = s.grads
             dy = BwdDy()
             if cp is not None:      # multiplicity weights, ragged groups, device-side row count
                 dy.wrow, dy.seg_grp, dy.rows_dev = cp.wrow.data_ptr(), cp.seg_grp.data_ptr(), cp.rows.data_ptr()
@@ -418,43 +395,17 @@ class SharedMLPMax(torch.autograd.Function):
                 nbp = lib.papc_xyz_bwd_parts(M)
                 bpart = torch.empty(nbp, cout, 4, device=dev, dtype=torch.float32)
                 check(lib.papc_xyz_l1_bwd_f32(ptr(dz), ptr(xc), ptr(wf), M, cout, ptr(bpart), st), "papc_xyz_l1_bwd_f32")
-                if inplace:
-                    dw0, acc0 = tgt[0].view(cout, cin), 1
-                else:
-                    dw0, acc0 = torch.empty(cout, cin, device=dev, dtype=torch.float32), 0
-                if gb_inplace != bool(acc0):       # (one accumulate flag for the three outputs: fall back to fresh gamma / beta buffers)
-                    dgb = torch.empty(2, cout, device=dev, dtype=torch.float32)
-                    dgamma_p, dbeta_p = dgb[0].data_ptr(), dgb[1].data_ptr()
-                    gb_fresh = True
-                else:
-                    gb_fresh = not gb_inplace
-                check(lib.papc_xyz_l1_bwd_finalize_f32(ptr(bpart), nbp, M, cout, ptr(gram), ptr(w), cin, 0, ptr(params[1]), cst[0].data_ptr(),
-                                                       cst[1].data_ptr(), cst[2].data_ptr(), dgamma_p, dbeta_p, ptr(dw0), acc0, st),
-                      "papc_xyz_l1_bwd_finalize_f32")
-                if not inplace:
-                    grads[0] = dw0.reshape(w.shape)
-                    grads[1] = None if (tgt is not None and tgt[1] is not None) else _lib.zeros((cout,), dev)
-                if gb_fresh:
-                    grads[2], grads[3] = dgb[0], dgb[1]
+                mean, invstd, scale, _ = cst_ptrs(cst)
+                check(lib.papc_xyz_l1_bwd_finalize_f32(ptr(bpart), nbp, M, cout, ptr(gram), ptr(w), cin, 0, ptr(params[1]), mean, invstd, scale,
+                                                       s.dgamma_p, s.dbeta_p, s.dw_p, s.acc_w, st), "papc_xyz_l1_bwd_finalize_f32")
+                s.zero_db()
                 break
-            dy.y = ptr(ys[l])
-            dy.mean, dy.invstd, dy.scale, dy.shift = (cst[i].data_ptr() for i in range(4))
-            dy.c1, dy.c2 = c12[0].data_ptr(), c12[1].data_ptr()
-            if fused_red is None:   # (sum p, sum p*xhat): separate pass, unless the dX kernel of layer l+1 already produced it
-                red, red_parts = torch.empty(n_parts, 2, cout, device=dev, dtype=torch.float32), n_parts
-                red_dz = ptr(ysel) if dy.dz_mode == DZ_MAX else dy.dz
-                if sparse_max and l == L - 1:     # the same pass also writes the sparse operand of this layer's dX / dW
-                    psel = torch.empty(M // spec.K, cout, device=dev, dtype=torch.float32)
-                    check(lib.papc_bn_bwd_reduce_max_f32(ptr(ysel), dy.gout, dy.K, dy.mean, dy.invstd, dy.scale, dy.shift, M, cout, n_parts,
-                                                         ptr(red), ptr(psel), st), "papc_bn_bwd_reduce_max_f32")
-                else:
-                    check(lib.papc_bn_bwd_reduce_f32(dy.dz_mode, red_dz, dy.gout, dy.argmax, dy.K, dy.y, dy.mean, dy.invstd, dy.scale,
-                                                     dy.shift, M, cout, n_parts, ptr(red), st), "papc_bn_bwd_reduce_f32")
-            else:
-                red, red_parts = fused_red, gemm_parts
-            check(lib.papc_bn_bwd_finalize_f32(ptr(red), red_parts, M, cout, dgamma_p, dbeta_p,
-                                               c12[0].data_ptr(), c12[1].data_ptr(), int(gb_inplace) | (2 if spec.eval_bn else 0), st),
-                  "papc_bn_bwd_finalize_f32")
+            dy.set_bn(ys[l], cst, c12)
+            # (sum p, sum p*xhat): a separate pass, unless the dX kernel of layer l+1 already produced them; under the sparse max the same
+            # pass also writes the sparse operand of this layer's dX / dW
+            psel = torch.empty(M // spec.K, cout, device=dev, dtype=torch.float32) if (sparse_max and l == L - 1) else None
+            bn_bwd_sums(dy, M, cout, c12, s.dgamma_p, s.dbeta_p, s.acc_gb, spec.eval_bn, dz=ptr(ysel) if dy.dz_mode == DZ_MAX else None,
+                        red=fused_red, psel=psel)
             if l == 0 and ctx.lin0:
                 # G[j] = sum of the dY rows that gathered point j (+ the xyz columns of dW, streamed); the D-wide products run on B*N rows
                 BN_ = spec.B * spec.N
@@ -466,34 +417,15 @@ class SharedMLPMax(torch.autograd.Function):
                 # the gradient lands in ONE [cout, cin] tensor -- the parameter's .grad view (accumulate) or a fresh one: the
                 # coordinate block and the feature block are summed straight into their column ranges (no concat, no add)
                 fcol0, xcol0 = (3, 0) if spec.xyz_first else (0, spec.D)
-                if inplace:
-                    dw, acc = tgt[0].view(cout, cin), 1
-                else:
-                    dw, acc = torch.empty(cout, cin, device=dev, dtype=torch.float32), 0
-                check(lib.papc_reduce_partials_strided_f32(ptr(dwx_part), parts_l, cout * 3, cout, 3, dw.data_ptr() + 4 * xcol0, cin, acc, st),
+                check(lib.papc_reduce_partials_strided_f32(ptr(dwx_part), parts_l, cout * 3, cout, 3, s.dw_p + 4 * xcol0, cin, s.acc_w, st),
                       "papc_reduce_partials_strided_f32")
-                # dW_f = G^T feats on the library's own dW kernel: G plays dY with BN constants that make dY = dz (scale 1, shift huge
-                # -> ReLU mask always on, c1 = c2 = 0)
-                one, zero, big = _lib.const_vec(1.0, cout, dev), _lib.const_vec(0.0, cout, dev), _lib.const_vec(1e30, cout, dev)
+                # dW_f = G^T feats on the library's own dW kernel: G plays dY with the identity constants (dY = dz); chunks of >= 64 rows
                 dyg = BwdDy()
                 dyg.dz_mode, dyg.dz, dyg.gout, dyg.argmax, dyg.K = DZ_DENSE, Gs.data_ptr(), None, None, 1
-                dyg.y = Gs.data_ptr()
-                dyg.mean, dyg.invstd, dyg.scale, dyg.shift = zero.data_ptr(), one.data_ptr(), one.data_ptr(), big.data_ptr()
-                dyg.c1, dyg.c2 = zero.data_ptr(), zero.data_ptr()
-                rpc_g = _dw_rows_per_chunk(BN_, cout, spec.D, 64)
-                n_chunks_g = (BN_ + rpc_g - 1) // rpc_g
-                pld_g = cout * spec.D + cout
-                part_g = torch.empty(n_chunks_g, pld_g, device=dev, dtype=torch.float32)
-                check(lib.papc_mlp_bwd_dw_f32(ctypes.byref(dyg), A_PLAIN, ptr(feats), spec.D, None, None, None, BN_, spec.D, cout, rpc_g,
-                                              part_g.data_ptr(), part_g.data_ptr() + 4 * cout * spec.D, pld_g, st), "papc_mlp_bwd_dw_f32")
-                check(lib.papc_reduce_partials_strided_f32(ptr(part_g), n_chunks_g, pld_g, cout, spec.D, dw.data_ptr() + 4 * fcol0, cin, acc,
-                                                           st), "papc_reduce_partials_strided_f32")
-                if not inplace:           # (db: a bias feeding a train-mode BN has gradient exactly 0)
-                    grads[0] = dw.reshape(w.shape)
-                    grads[1] = None if (tgt is not None and tgt[1] is not None) else _lib.zeros((cout,), dev)   # (exact 0: nothing to add in place)
-                    if not gb_inplace:
-                        grads[2] = dgb[0]
-                        grads[3] = dgb[1]
+                identity_bn(dyg, Gs, cout, dev)
+                DwPartials(dyg, A_PLAIN, ptr(feats), spec.D, None, None, None, BN_, spec.D, cout, dev, min_rows=64).fold_cols(
+                    s.dw_p + 4 * fcol0, cin, s.acc_w)
+                s.zero_db()
                 if ctx.feats_needs_grad:
                     # grad_feats = G W_f: the same row GEMM with the transposed feature block as its weight
                     wt_full = ctx.wt_table.get(w.data_ptr()) if ctx.wt_table is not None else None
@@ -521,62 +453,28 @@ class SharedMLPMax(torch.autograd.Function):
                 # no stored output: T = P'^T A, the Gram matrix of the input rows and their column sums in one pass, closed form for dW
                 pc = consts[l - 1]
                 ws = torch.empty(lib.papc_mlp_bwd_dw_max_ws_floats(M, cin, cout), device=dev, dtype=torch.float32)
-                if inplace:
-                    dw, acc = tgt[0].view(cout, cin), 1
-                else:
-                    dw, acc = torch.empty(cout, cin, device=dev, dtype=torch.float32), 0
                 check(lib.papc_mlp_bwd_dw_max_f32(ptr(max_prep[0]), ptr(argmax), spec.K, ys[l - 1].data_ptr(), pc[2].data_ptr(), pc[3].data_ptr(),
                                                   ptr(w), max_prep[3][0].data_ptr(), cst[2].data_ptr(), c12[0].data_ptr(), M, cin, cout,
-                                                  ptr(ws), ptr(dw), acc, st), "papc_mlp_bwd_dw_max_f32")
-                if not inplace:
-                    grads[4 * l + 0] = dw.reshape(w.shape)
-                    grads[4 * l + 1] = None if (tgt is not None and tgt[1] is not None) else _lib.zeros((cout,), dev)   # (exact 0 under a train-mode BN)
-                    if not gb_inplace:
-                        grads[4 * l + 2] = dgb[0]
-                        grads[4 * l + 3] = dgb[1]
+                                                  ptr(ws), s.dw_p, s.acc_w, st), "papc_mlp_bwd_dw_max_f32")
+                s.zero_db()
             x1 = xyz1 and l == 1             # the input of this layer is the recomputed activation of the coordinates-only first layer
             if not (ctx.nostore and l == L - 1):
-                rpc = 0
-                if l > 0:                        # (the kernel's own preference where it has one: papc_mlp_bwd_dw_chunk_hint)
-                    rpc = lib.papc_mlp_bwd_dw_chunk_hint(M, cin, cout, A_XYZ if x1 else A_BNRELU, dy.dz_mode, spec.K if dy.dz_mode == DZ_MAX else 0)
-                elif not plain:
-                    rpc = lib.papc_mlp_bwd_dw_chunk_hint(M, cin, cout, A_GROUP, dy.dz_mode, spec.K if dy.dz_mode == DZ_MAX else 0)
-                if rpc <= 0:
-                    rpc = _dw_rows_per_chunk(M, cout, cin)
-                n_chunks = (M + rpc - 1) // rpc
-                pld = cout * cin + cout          # one partial buffer: chunk rows are [dW (cout*cin) | db (cout)]
-                part = torch.empty(n_chunks, pld, device=dev, dtype=torch.float32)
-                dwp_p, dbp_p = part.data_ptr(), part.data_ptr() + 4 * cout * cin
                 if l == 0 and plain:
-                    check(lib.papc_mlp_bwd_dw_f32(ctypes.byref(dy), A_PLAIN, ptr(x_rows), cin, None, None, None, M, cin, cout, rpc,
-                                                  dwp_p, dbp_p, pld, st), "papc_mlp_bwd_dw_f32")
+                    a_op = (A_PLAIN, ptr(x_rows), cin, None, None, None)
                 elif l == 0:
-                    check(lib.papc_mlp_bwd_dw_f32(ctypes.byref(dy), A_GROUP, None, 0, ctypes.byref(grp), None, None, M, cin, cout, rpc,
-                                                  dwp_p, dbp_p, pld, st), "papc_mlp_bwd_dw_f32")
+                    a_op = (A_GROUP, None, 0, ctypes.byref(grp), None, None)
                 elif x1:
-                    check(lib.papc_mlp_bwd_dw_f32(ctypes.byref(dy), A_XYZ, ptr(xc), 4, None, ptr(wf), None, M, cin, cout, rpc, dwp_p, dbp_p, pld, st),
-                          "papc_mlp_bwd_dw_f32")
+                    a_op = (A_XYZ, ptr(xc), 4, None, ptr(wf), None)
                 else:
                     pc = consts[l - 1]
-                    check(lib.papc_mlp_bwd_dw_f32(ctypes.byref(dy), A_BNRELU, ys[l - 1].data_ptr(), cin, None, pc[2].data_ptr(),
-                                                  pc[3].data_ptr(), M, cin, cout, rpc, dwp_p, dbp_p, pld, st), "papc_mlp_bwd_dw_f32")
+                    a_op = (A_BNRELU, ys[l - 1].data_ptr(), cin, None, pc[2].data_ptr(), pc[3].data_ptr())
+                part = DwPartials(dy, *a_op, M, cin, cout, dev)
                 # the partials of all layers are folded in ONE launch once the stack's last dW kernel is enqueued (papc_reduce_partials_batch_f32)
-                if inplace:
-                    reduce_jobs.append((part, n_chunks, pld, cout * cin, tgt[0].data_ptr(), cout, tgt[1].data_ptr(), 1))
-                else:
-                    dw = torch.empty(cout, cin, device=dev, dtype=torch.float32)
-                    db = torch.empty(cout, device=dev, dtype=torch.float32)
-                    if spec.eval_bn:      # no batch-mean term removes the bias direction: db = sum_m dy = scale * sum_m p (tiny [C] op)
-                        check(lib.papc_reduce_partials2_f32(ptr(part), n_chunks, pld, cout * cin, ptr(dw), cout, ptr(db), 0, st),
-                              "papc_reduce_partials2_f32")
-                        db = cst[2] * dgb[1]
-                    else:
-                        reduce_jobs.append((part, n_chunks, pld, cout * cin, dw.data_ptr(), cout, db.data_ptr(), 0))
-                    grads[4 * l + 0] = dw.reshape(w.shape)
-                    grads[4 * l + 1] = None if (tgt is not None and tgt[1] is not None and not spec.eval_bn) else db
-                    if not gb_inplace:
-                        grads[4 * l + 2] = dgb[0]
-                        grads[4 * l + 3] = dgb[1]
+                if s.acc_w or not spec.eval_bn:
+                    reduce_jobs.append((part, (s.dw_p, s.db_p, s.acc_w)))
+                else:                     # no batch-mean term removes the bias direction: db = sum_m dy = scale * sum_m p (tiny [C] op)
+                    part.fold(s.dw_p, s.db_p, 0)
+                    grads[4 * l + 1] = cst[2] * grads[4 * l + 3]
             # ---- dX
             fused_red = None
             if l > 0:
@@ -585,11 +483,10 @@ class SharedMLPMax(torch.autograd.Function):
                 # the dX kernel also accumulates layer l-1's BN-backward reductions over the dz it produces
                 nr_ref = None
                 if _FUSE_RED and not x1:     # (x1: the layer below takes its BN-backward sums from its own pass over dz, xyz1.hip)
-                    pc = consts[l - 1]
                     fused_red = torch.empty(gemm_parts, 2, cin, device=dev, dtype=torch.float32)
                     nr = BwdRed()
                     nr.y = ys[l - 1].data_ptr()
-                    nr.mean, nr.invstd, nr.scale, nr.shift = (pc[i].data_ptr() for i in range(4))
+                    nr.mean, nr.invstd, nr.scale, nr.shift = cst_ptrs(consts[l - 1])
                     nr.red_partial = fused_red.data_ptr()
                     nr_ref = ctypes.byref(nr)
                 if sparse_max and l == L - 1:
@@ -614,33 +511,8 @@ class SharedMLPMax(torch.autograd.Function):
                 sc.N, sc.S, sc.K, sc.D = spec.N, spec.S, spec.K, spec.D
                 sc.col0 = 3 if spec.xyz_first else 0
                 check(lib.papc_mlp_bwd_dx_f32(ctypes.byref(dy), ptr(wt), M, cin, cout, None, ctypes.byref(sc), None, st), "papc_mlp_bwd_dx_f32")
-        for k0 in range(0, len(reduce_jobs), 8):       # (at most 8 jobs per launch)
-            chunk = reduce_jobs[k0:k0 + 8]
-            jobs = (ReduceJob * len(chunk))()
-            for j, (part_t, nch, ld_, n1_, o1, n2_, o2, acc_) in zip(jobs, chunk):
-                j.partial, j.n_chunks, j.accumulate, j.ld, j.n1, j.n2, j.out1, j.out2 = part_t.data_ptr(), nch, acc_, ld_, n1_, n2_, o1, o2
-            check(lib.papc_reduce_partials_batch_f32(jobs, len(chunk), st), "papc_reduce_partials_batch_f32")
+        launch_batched(ReduceJob, [p.job(*out) for p, out in reduce_jobs], lib.papc_reduce_partials_batch_f32, "papc_reduce_partials_batch_f32")
         return (None, None, None, None, grad_feats, None, grad_x) + tuple(grads)
-
-
-def grad_targets_of(params):
-    """Per parameter: its .grad tensor when the parameter opted in to in-place accumulation (a view of distributed.FlatParams.grad),
-    else None -- or None altogether when no parameter did.  With a target the backward adds the gradient in place (one fused accumulate
-    in the reduce kernels) and hands autograd ``None`` for it: no per-parameter AccumulateGrad add kernels.  Entries that are not
-    opted-in leaf Parameters (e.g. the zero-padded view of a first conv weight, layers._pad_features) go back through autograd as usual."""
-    tg = []
-    for p in params:
-        g = None
-        # explicit opt-in (distributed.FlatParams marks its parameters): writing .grad behind autograd's back skips AccumulateGrad
-        # hooks, so torch's DistributedDataParallel, post-accumulate hooks, torch.autograd.grad() and checkpoint recomputation would
-        # miss or double-count these gradients -- a parameter that merely HAS a .grad (second step of any plain optimizer loop) does
-        # not qualify
-        if isinstance(p, torch.nn.Parameter) and getattr(p, "_papc_inplace_grad", False):
-            g = p.grad
-            if not (p.requires_grad and g is not None and g.is_contiguous() and g.dtype == torch.float32 and g.shape == p.shape):
-                g = None
-        tg.append(g)
-    return tg if any(t is not None for t in tg) else None
 
 
 def shared_mlp_max(spec, bn_buffers, xyz, new_xyz, feats, idx, params, x_rows=None):

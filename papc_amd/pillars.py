@@ -21,7 +21,9 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
+from .linear import linear_rows
 from .mlp import StackSpec, shared_mlp_max
+from .nodeparts import all_or_none, grad_targets_of
 
 
 class PfnDesc(ctypes.Structure):
@@ -57,7 +59,6 @@ class _PFNFused(torch.autograd.Function):
         check(lib.papc_pfn_fwd(ctypes.byref(d), ctypes.byref(io), stream_ptr()), "papc_pfn_fwd")
         ctx.desc, ctx.saved = d, saved
         ctx.bufs = (rmean, rvar, tickets)
-        from .mlp import grad_targets_of
         ctx.grad_targets = grad_targets_of([w, gamma, beta]) if torch.is_grad_enabled() or w.requires_grad else None
         ctx.save_for_backward(features, num_voxels, coors, w, gamma, beta)
         return out
@@ -74,17 +75,10 @@ class _PFNFused(torch.autograd.Function):
         scratch = torch.empty(wb.value, device=dev, dtype=torch.uint8)
         io = PfnIo(ptr(features), ptr(num_voxels), ptr(coors), ptr(w), ptr(gamma), ptr(beta), ptr(ctx.bufs[0]), ptr(ctx.bufs[1]), None, ptr(ctx.saved),
                    ptr(scratch), ptr(ctx.bufs[2]))
-        tg = ctx.grad_targets            # (w.grad, gamma.grad, beta.grad) of parameters that opted in to in-place accumulation, or None
-        if tg is not None and any(t is None for t in tg):
-            tg = None
-        if tg is not None:
-            check(lib.papc_pfn_bwd(ctypes.byref(d), ctypes.byref(io), ptr(gout), tg[0].data_ptr(), tg[1].data_ptr(), tg[2].data_ptr(), 1, stream_ptr()),
-                  "papc_pfn_bwd")
-            return (None,) * 14
-        dgb = torch.empty(2, d.C, device=dev, dtype=torch.float32)
-        dw = torch.empty(d.C, 9, device=dev, dtype=torch.float32)
-        check(lib.papc_pfn_bwd(ctypes.byref(d), ctypes.byref(io), ptr(gout), ptr(dw), dgb[0].data_ptr(), dgb[1].data_ptr(), 0, stream_ptr()), "papc_pfn_bwd")
-        return None, None, None, None, dw, dgb[0], dgb[1], None, None, None, None, None, None, None
+        # (w.grad, gamma.grad, beta.grad) of parameters that opted in to in-place accumulation, or fresh tensors
+        (dw, dgamma, dbeta), acc, grads = all_or_none(ctx.grad_targets, [(d.C, 9), (d.C,), (d.C,)], dev)
+        check(lib.papc_pfn_bwd(ctypes.byref(d), ctypes.byref(io), ptr(gout), ptr(dw), ptr(dgamma), ptr(dbeta), acc, stream_ptr()), "papc_pfn_bwd")
+        return (None,) * 4 + grads + (None,) * 7
 
 
 class _GroupMax(torch.autograd.Function):
@@ -96,8 +90,7 @@ class _GroupMax(torch.autograd.Function):
         lib = _lib.load()
         C = x.shape[1]
         dev = x.device
-        one = torch.ones(C, device=dev, dtype=torch.float32)
-        zero = torch.zeros(C, device=dev, dtype=torch.float32)
+        one, zero = _lib.const_vec(1.0, C, dev), _lib.const_vec(0.0, C, dev)
         out = torch.empty(G, C, device=dev, dtype=torch.float32)
         argmax = torch.empty(G, C, device=dev, dtype=torch.int32)
         check(lib.papc_bn_relu_max_f32(ptr(x), ptr(one), ptr(zero), G, K, C, ptr(out), ptr(argmax), stream_ptr()), "papc_bn_relu_max_f32")
@@ -113,76 +106,6 @@ class _GroupMax(torch.autograd.Function):
         dx = torch.empty(G * ctx.K, C, device=gout.device, dtype=torch.float32)
         check(_lib.load().papc_group_max_bwd_f32(ptr(gout), ptr(argmax), G, ctx.K, C, ptr(dx), stream_ptr()), "papc_group_max_bwd_f32")
         return dx, None, None
-
-
-class _LinearReLU(torch.autograd.Function):
-    """relu(rows @ w^T + b) without a norm (PFNLayer(use_norm=False): Linear with bias + the Empty norm, pillars.py:25-27,:30-32) on the
-    MFMA row kernels.  The backward reuses the BN-aware kernels with identity constants (scale 1, shift 0, mean 0, invstd 1,
-    c1 = c2 = 0): their dY is then exactly gout * [y > 0]."""
-
-    @staticmethod
-    def forward(ctx, rows, w, b):
-        lib = _lib.load()
-        st = stream_ptr()
-        M, cin = rows.shape
-        cout = w.shape[0]
-        dev = rows.device
-        y = torch.empty(M, cout, device=dev, dtype=torch.float32)
-        check(lib.papc_mlp_gemm_f32(0, ptr(rows), cin, None, None, None, ptr(w), ptr(b), M, cin, cout, ptr(y), None, None, st),
-              "papc_mlp_gemm_f32")
-        ident = torch.zeros(4, cout, device=dev, dtype=torch.float32)    # mean 0, invstd / scale 1, shift 0
-        ident[1].fill_(1.0)
-        ident[2].fill_(1.0)
-        x = torch.empty(M, cout, device=dev, dtype=torch.float32)
-        check(lib.papc_bn_relu_f32(ptr(y), ident[2].data_ptr(), ident[3].data_ptr(), M, cout, ptr(x), st), "papc_bn_relu_f32")
-        ctx.save_for_backward(rows, w, y, ident)
-        ctx.needs = (rows.requires_grad, )
-        return x
-
-    @staticmethod
-    def backward(ctx, gout):
-        from ._lib import BwdDy
-        from .mlp import _dw_rows_per_chunk
-        import ctypes
-        lib = _lib.load()
-        st = stream_ptr()
-        rows, w, y, ident = ctx.saved_tensors
-        M, cin = rows.shape
-        cout = w.shape[0]
-        dev = rows.device
-        gout = gout.contiguous().float()
-        zero2 = torch.zeros(2, cout, device=dev, dtype=torch.float32)
-        dy = BwdDy()
-        dy.dz_mode, dy.dz, dy.gout, dy.argmax, dy.K = 0, gout.data_ptr(), None, None, 1
-        dy.y = y.data_ptr()
-        dy.mean, dy.invstd, dy.scale, dy.shift = ident[0].data_ptr(), ident[1].data_ptr(), ident[2].data_ptr(), ident[3].data_ptr()
-        dy.c1, dy.c2 = zero2[0].data_ptr(), zero2[1].data_ptr()
-        rpc = _dw_rows_per_chunk(M, cout, cin)
-        n_chunks = (M + rpc - 1) // rpc
-        pld = cout * cin + cout
-        part = torch.empty(n_chunks, pld, device=dev, dtype=torch.float32)
-        check(lib.papc_mlp_bwd_dw_f32(ctypes.byref(dy), 0, ptr(rows), cin, None, None, None, M, cin, cout, rpc, part.data_ptr(),
-                                      part.data_ptr() + 4 * cout * cin, pld, st), "papc_mlp_bwd_dw_f32")
-        dw = torch.empty(cout, cin, device=dev, dtype=torch.float32)
-        dbz = torch.empty(cout, device=dev, dtype=torch.float32)
-        check(lib.papc_reduce_partials2_f32(ptr(part), n_chunks, pld, cout * cin, ptr(dw), cout, ptr(dbz), 0, st), "papc_reduce_partials2_f32")
-        # the dW kernel writes the bias gradient of a BN-fed conv (exactly 0); without a norm it is the column sum of dY:
-        # (sum p, sum p*xhat) from the BN-backward reduce with the identity constants -> its first row
-        n_parts = min(512, (M + 127) // 128)
-        red = torch.empty(n_parts, 2, cout, device=dev, dtype=torch.float32)
-        check(lib.papc_bn_bwd_reduce_f32(0, ptr(gout), None, None, 1, ptr(y), ident[0].data_ptr(), ident[1].data_ptr(), ident[2].data_ptr(),
-                                         ident[3].data_ptr(), M, cout, n_parts, ptr(red), st), "papc_bn_bwd_reduce_f32")
-        dgb = torch.empty(2, cout, device=dev, dtype=torch.float32)
-        c12 = torch.empty(2, cout, device=dev, dtype=torch.float32)
-        check(lib.papc_bn_bwd_finalize_f32(ptr(red), n_parts, M, cout, dgb[0].data_ptr(), dgb[1].data_ptr(), c12[0].data_ptr(),
-                                           c12[1].data_ptr(), 2, st), "papc_bn_bwd_finalize_f32")
-        db = dgb[1]
-        dx = None
-        if ctx.needs[0]:
-            wt = w.t().contiguous()
-            dx = torch.empty(M, cin, device=dev, dtype=torch.float32)
-            check(lib.papc_mlp_bwd_dx_f32(ctypes.byref(dy), ptr(wt), M, cin, cout, ptr(dx), None, None, st), "papc_mlp_bwd_dx_f32")
-        return dx, dw, db
 
 
 class PFNLayer(nn.Module):
@@ -207,7 +130,8 @@ class PFNLayer(nn.Module):
         """relu(norm(linear(rows))) for rows [M, Cin] -> [M, C] (:30-32), differentiable."""
         C = self.units
         if not self.use_norm:
-            return _LinearReLU.apply(rows, self.linear.weight, self.linear.bias)
+            # Linear with bias + the Empty norm (pillars.py:25-27): its gradients go back through autograd
+            return linear_rows(rows, self.linear.weight, self.linear.bias, relu=True, inplace=False)
         M = rows.shape[0]
         spec = StackSpec(1, M, M, 1, 0, True, eps=self.norm.eps, momentum=self.norm.momentum, pool=False,
                          eval_bn=not self.training)

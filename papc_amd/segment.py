@@ -15,7 +15,8 @@ import os
 import torch
 
 from . import _lib
-from ._lib import check, ptr, stream_ptr
+from ._lib import BwdDy, check, cst_ptrs, ptr, stream_ptr
+from .nodeparts import bn_bwd_sums
 
 _SEG_CONCAT = os.environ.get("PAPC_SEG_CONCAT", "1") != "0"   # A/B switch: 0 = the materialised concat on the shared-MLP stack
 MOMENTUM = 0.9                                                # paddle's BatchNorm momentum (r = 0.9 r + 0.1 batch), as every norm here
@@ -40,7 +41,7 @@ class _CloudConcatBnRelu(torch.autograd.Function):
         y = torch.empty(M, cout, device=dev, dtype=torch.float32)
         cvec = torch.empty(B, cout, device=dev, dtype=torch.float32)
         consts = torch.empty(4, cout, device=dev, dtype=torch.float32)       # mean, invstd, scale, shift
-        mean, invstd, scale, shift = (ptr(consts[i]) for i in range(4))
+        mean, invstd, scale, shift = cst_ptrs(consts)
         if training:
             parts = lib.papc_cloud_concat_conv_parts(B, N)
             stats = torch.empty(parts, 2, cout, device=dev, dtype=torch.float32)
@@ -70,21 +71,18 @@ class _CloudConcatBnRelu(torch.autograd.Function):
         st = stream_ptr()
         dev = y.device
         gz = gz.contiguous().float()
-        mean, invstd, scale, shift = (ptr(consts[i]) for i in range(4))
-        n_parts = min(512, (M + 127) // 128)
-        red = torch.empty(n_parts, 2, cout, device=dev, dtype=torch.float32)
-        check(lib.papc_bn_bwd_reduce_f32(0, ptr(gz), None, None, 1, ptr(y), mean, invstd, scale, shift, M, cout, n_parts, ptr(red), st),
-              "papc_bn_bwd_reduce_f32")
         bn_g = torch.empty(4, cout, device=dev, dtype=torch.float32)         # dgamma, dbeta, c1, c2
-        check(lib.papc_bn_bwd_finalize_f32(ptr(red), n_parts, M, cout, ptr(bn_g[0]), ptr(bn_g[1]), ptr(bn_g[2]), ptr(bn_g[3]), 2 if ctx.eval_bn else 0, st),
-              "papc_bn_bwd_finalize_f32")
+        dy = BwdDy()
+        dy.dz_mode, dy.dz, dy.K = 0, ptr(gz), 1
+        dy.set_bn(y, consts, bn_g[2:])
+        bn_bwd_sums(dy, M, cout, bn_g[2:], ptr(bn_g[0]), ptr(bn_g[1]), eval_bn=ctx.eval_bn)
         dx = torch.empty(M, cp, device=dev, dtype=torch.float32) if ctx.needs_input_grad[0] else None
         dg = torch.empty(B, cg, device=dev, dtype=torch.float32) if ctx.needs_input_grad[1] else None
         dw = torch.empty(cout, cp + cg, device=dev, dtype=torch.float32)
         db = torch.empty(cout, device=dev, dtype=torch.float32) if ctx.has_bias else None
         nbytes = lib.papc_cloud_concat_conv_bwd_workspace(B, N, cp, cg, cout)
         ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        check(lib.papc_cloud_concat_conv_bwd_f32(ptr(gz), ptr(y), mean, invstd, scale, shift, ptr(bn_g[2]), ptr(bn_g[3]), ptr(x), x.stride(0), ptr(g),
+        check(lib.papc_cloud_concat_conv_bwd_f32(ptr(gz), ptr(y), dy.mean, dy.invstd, dy.scale, dy.shift, dy.c1, dy.c2, ptr(x), x.stride(0), ptr(g),
                                                  ptr(w), B, N, cp, cg, cout, ptr(dx), cp, 0, ptr(dw), ptr(db), ptr(dg), None, ptr(ws), nbytes, st),
               "papc_cloud_concat_conv_bwd_f32")
         return dx, dg, dw, db, bn_g[0], bn_g[1], None, None, None, None, None

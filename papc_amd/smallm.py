@@ -17,7 +17,8 @@ import os
 import torch
 
 from . import _lib
-from ._lib import check, ptr, stream_ptr
+from ._lib import check, cst_ptrs, ptr, stream_ptr
+from .nodeparts import LayerSlots, launch_batched
 
 PLAIN, CONCAT, BNRELU, DY_DENSE, DY_MAX = 0, 1, 2, 3, 4
 DZ_DENSE = 0                                            # papc_bwd_dy.dz_mode of a dense upstream gradient (PAPC_DZ_DENSE)
@@ -136,12 +137,7 @@ class PlanesMLPMax(torch.autograd.Function):
                 rows, off = (ch[l], 0) if l > 0 else (n_in, fcol0)
                 wtp[l] = _planes(lib, rows, ch[l + 1], dev)
                 jobs.append((w2.data_ptr() + 4 * off, 1, ch[l], rows, ch[l + 1], wtp[l].data_ptr()))
-        for j0 in range(0, len(jobs), 8):
-            chunk = jobs[j0:j0 + 8]
-            arr = (PgWJob * len(chunk))()
-            for a, (src, sr, sc, R, K, dst) in zip(arr, chunk):
-                a.src, a.row_stride, a.col_stride, a.R, a.K, a.planes = src, sr, sc, R, K, dst
-            check(lib.papc_pg_prep_weights_f32(arr, len(chunk), st), "papc_pg_prep_weights_f32")
+        launch_batched(PgWJob, jobs, lib.papc_pg_prep_weights_f32, "papc_pg_prep_weights_f32")
 
         # ---- layer 1 operand: the rows of sample_and_group_all (or the caller's rows)
         def prep(**kw):
@@ -244,25 +240,21 @@ class PlanesMLPMax(torch.autograd.Function):
         for l in range(L - 1, -1, -1):
             cout, cin = ch[l + 1], ch[l]
             cst = consts[l]
-            tgt = spec.grad_targets[4 * l: 4 * l + 4] if spec.grad_targets is not None else None
-            inplace = tgt is not None and all(t is not None for t in tgt)
-            gb_inplace = tgt is not None and tgt[2] is not None and tgt[3] is not None
-            if gb_inplace:
-                dgamma_p, dbeta_p = tgt[2].data_ptr(), tgt[3].data_ptr()
-            else:
-                dgb = torch.empty(2, cout, device=dev, dtype=torch.float32)
-                dgamma_p, dbeta_p = dgb[0].data_ptr(), dgb[1].data_ptr()
+            s = LayerSlots(spec.grad_targets, l, params[4 * l], spec.eval_bn)
+            s.zero_db()                                        # (no kernel here writes db)
+            grads[4 * l: 4 * l + 4] = s.grads
+            mean, invstd, scale, shift = cst_ptrs(cst)
             need_dx = l > 0 or ctx.in_grad
             # dY of this layer as planes, both orientations; c1 / c2 / dgamma / dbeta folded in the prologue
             dyp = _planes(lib, M, cout, dev) if need_dx else None
             dypt = _planes(lib, cout, M, dev)
-            common = dict(M=M, C=cout, x=ys[l].data_ptr(), ldx=cout, mean=cst[0].data_ptr(), invstd=cst[1].data_ptr(), scale=cst[2].data_ptr(),
-                          shift=cst[3].data_ptr(), dgamma=dgamma_p, dbeta=dbeta_p, accumulate=int(gb_inplace), planes=ptr(dyp), planes_t=dypt.data_ptr())
+            common = dict(M=M, C=cout, x=ys[l].data_ptr(), ldx=cout, mean=mean, invstd=invstd, scale=scale, shift=shift,
+                          dgamma=s.dgamma_p, dbeta=s.dbeta_p, accumulate=s.acc_gb, planes=ptr(dyp), planes_t=dypt.data_ptr())
             if l == L - 1 and not spec.pool:
                 # dense upstream gradient: the layer's BN-backward sums in a pass of their own (T partial rows, folded in the prep's prologue)
                 red = torch.empty(T, 2, cout, device=dev, dtype=torch.float32)
-                check(lib.papc_bn_bwd_reduce_f32(DZ_DENSE, gout.data_ptr(), None, None, 1, ys[l].data_ptr(), cst[0].data_ptr(), cst[1].data_ptr(),
-                                                 cst[2].data_ptr(), cst[3].data_ptr(), M, cout, T, red.data_ptr(), st), "papc_bn_bwd_reduce_f32")
+                check(lib.papc_bn_bwd_reduce_f32(DZ_DENSE, gout.data_ptr(), None, None, 1, ys[l].data_ptr(), mean, invstd, scale, shift, M, cout, T,
+                                                 red.data_ptr(), st), "papc_bn_bwd_reduce_f32")
                 prep(mode=DY_DENSE, dz=gout.data_ptr(), red=red.data_ptr(), red_parts=T, **common)
             elif l == L - 1:
                 prep(mode=DY_MAX, gout=gout.data_ptr(), ysel=ysel.data_ptr(), argmax=argmax.data_ptr(), K=GROUP, **common)
@@ -273,14 +265,13 @@ class PlanesMLPMax(torch.autograd.Function):
             gs = (PgGemm * 2)()
             ng = 0
             if l > 0:
-                pc = consts[l - 1]
                 dz_prev = torch.empty(M, cin, device=dev, dtype=torch.float32)
                 red_prev = torch.empty(T, 2, cin, device=dev, dtype=torch.float32)
                 g = gs[ng]
                 ng += 1
                 g.epi, g.a, g.b, g.R1, g.R2, g.K = EPI_RED, dyp.data_ptr(), wtp[l].data_ptr(), M, cin, cout
                 g.c, g.ldc, g.split, g.split_stride, g.stats, g.family = dz_prev.data_ptr(), cin, 1, 0, red_prev.data_ptr(), K_BWD_DX
-                g.y_prev, g.mean, g.invstd, g.scale, g.shift = ys[l - 1].data_ptr(), pc[0].data_ptr(), pc[1].data_ptr(), pc[2].data_ptr(), pc[3].data_ptr()
+                g.y_prev, (g.mean, g.invstd, g.scale, g.shift) = ys[l - 1].data_ptr(), cst_ptrs(consts[l - 1])
             elif ctx.in_grad:
                 n_in = ctx.n_in
                 grad_in = torch.empty(M, n_in, device=dev, dtype=torch.float32)
@@ -296,25 +287,10 @@ class PlanesMLPMax(torch.autograd.Function):
             g.epi, g.a, g.b, g.R1, g.R2, g.K = EPI_STORE, dypt.data_ptr(), PT[l].data_ptr(), cout, cin, M
             g.c, g.ldc, g.split, g.split_stride, g.family = part.data_ptr(), cin, split, cout * cin, K_BWD_DW
             check(lib.papc_pg_gemm_group_f32(gs, ng, st), "papc_pg_gemm_group_f32")
-            if inplace:
-                fold.append((part.data_ptr(), split, cout * cin, cout * cin, tgt[0].data_ptr(), 1))
-            else:
-                dw = torch.empty(cout, cin, device=dev, dtype=torch.float32)
-                fold.append((part.data_ptr(), split, cout * cin, cout * cin, dw.data_ptr(), 0))
-                grads[4 * l + 0] = dw.reshape(params[4 * l].shape)
-                # a bias feeding a train-mode BN has gradient exactly 0
-                grads[4 * l + 1] = None if (tgt is not None and tgt[1] is not None) else _lib.zeros((cout,), dev)
-                if not gb_inplace:
-                    grads[4 * l + 2] = dgb[0]
-                    grads[4 * l + 3] = dgb[1]
+            fold.append((part.data_ptr(), split, cout * cin, cout * cin, s.dw_p, s.acc_w))
             if l > 0:
                 dz, red = dz_prev, red_prev
-        for j0 in range(0, len(fold), 8):
-            chunk = fold[j0:j0 + 8]
-            arr = (PgFoldJob * len(chunk))()
-            for a, (pp, ns, stride, n, outp, acc) in zip(arr, chunk):
-                a.partial, a.nsplit, a.stride, a.n, a.out, a.accumulate = pp, ns, stride, n, outp, acc
-            check(lib.papc_pg_fold_f32(arr, len(chunk), st), "papc_pg_fold_f32")
+        launch_batched(PgFoldJob, fold, lib.papc_pg_fold_f32, "papc_pg_fold_f32")
         grad_feats = grad_x = None
         if grad_in is not None:
             if ctx.plain:

@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
+from .nodeparts import LayerSlots
 
 MAXL = 8
 c_p, c_i, c_l, c_f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
@@ -224,28 +225,11 @@ class SharedMLPStack(torch.autograd.Function):
             w = params[4 * l]
             cout = w.shape[0]
             cin = w.numel() // cout
-            tgt = spec.grad_targets[4 * l: 4 * l + 4] if spec.grad_targets is not None else None
-            inplace = tgt is not None and all(t is not None for t in tgt)
-            gb_inplace = tgt is not None and tgt[2] is not None and tgt[3] is not None and not spec.eval_bn
-            all_inplace = all_inplace and inplace
-            if inplace:          # accumulate straight into the parameters' .grad (flat-bucket views): no autograd add kernels
-                g.dw[l], g.db[l], g.acc_w[l] = tgt[0].data_ptr(), tgt[1].data_ptr(), 1
-            else:
-                dw = torch.empty(cout, cin, device=dev, dtype=torch.float32)
-                grads[4 * l] = dw.reshape(w.shape)
-                g.dw[l], g.acc_w[l] = dw.data_ptr(), 0
-                if tgt is not None and tgt[1] is not None and not spec.eval_bn:
-                    g.db[l] = None                      # (a bias under a train-mode BN: gradient exactly 0 -- nothing to add in place)
-                else:
-                    db = torch.empty(cout, device=dev, dtype=torch.float32)
-                    grads[4 * l + 1] = db
-                    g.db[l] = db.data_ptr()
-            if gb_inplace and not (l == 0 and plan.xyz1 and not inplace):
-                g.dgamma[l], g.dbeta[l], g.acc_gb[l] = tgt[2].data_ptr(), tgt[3].data_ptr(), 1
-            else:                # (the coordinates-only first layer takes one accumulate flag for its three outputs)
-                dgb = torch.empty(2, cout, device=dev, dtype=torch.float32)
-                grads[4 * l + 2], grads[4 * l + 3] = dgb[0], dgb[1]
-                g.dgamma[l], g.dbeta[l], g.acc_gb[l] = dgb[0].data_ptr(), dgb[1].data_ptr(), 0
+            s = LayerSlots(spec.grad_targets, l, w, spec.eval_bn, xyz_first_layer=(l == 0 and bool(plan.xyz1)))
+            all_inplace = all_inplace and bool(s.acc_w)
+            g.dw[l], g.db[l], g.acc_w[l] = s.dw_p, s.db_p, s.acc_w
+            g.dgamma[l], g.dbeta[l], g.acc_gb[l] = s.dgamma_p, s.dbeta_p, s.acc_gb
+            grads[4 * l: 4 * l + 4] = s.grads
             if ctx.wt_table is not None:
                 t = ctx.wt_table.get(w.data_ptr())
                 if t is not None and tuple(t.shape) == (cin, cout):

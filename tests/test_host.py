@@ -177,3 +177,45 @@ def test_deferred_fold_list_survives_a_backward_that_raises(monkeypatch):
     assert launched[-1][1] == 2
     assert all(q.keep == ["scratch"] or (q.done and not q.keep) for q in stale)
     folds._live.clear()
+
+
+def test_per_layer_gradient_slots():
+    """nodeparts.LayerSlots: which of a layer's four gradients (w, b, gamma, beta) are added in place into their targets and which go back
+    through autograd.  No library, no device: the rule is host code."""
+    from papc_amd.nodeparts import LayerSlots
+    cout, cin = 6, 5
+    w = torch.zeros(cout, cin, 1, 1)
+    tw, tb, tg, tbe = torch.zeros(cout, cin, 1, 1), torch.zeros(cout), torch.zeros(cout), torch.zeros(cout)
+    IN, FRESH, NOTHING = "in place", "fresh", "nothing"
+    # (name, targets, eval_bn, coordinates-only first layer) -> where (dW, db, dgamma / dbeta) go, acc_w, acc_gb
+    table = [
+        ("no targets", None, False, False, (FRESH, FRESH, FRESH), 0, 0),
+        ("all four", [tw, tb, tg, tbe], False, False, (IN, IN, IN), 1, 1),
+        ("gamma and beta only (padded first conv)", [None, None, tg, tbe], False, False, (FRESH, FRESH, IN), 0, 1),
+        ("w, gamma, beta but no b", [tw, None, tg, tbe], False, False, (FRESH, FRESH, IN), 0, 1),
+        ("all four, eval_bn", [tw, tb, tg, tbe], True, False, (IN, IN, FRESH), 1, 0),
+        ("gamma and beta only, coordinates-only first layer", [None, None, tg, tbe], False, True, (FRESH, FRESH, FRESH), 0, 0),
+        # (beyond the six cases: a bias target without a full set under a train-mode norm -- the gradient is an exact zero, nothing is written)
+        ("b, gamma, beta but no w", [None, tb, tg, tbe], False, False, (FRESH, NOTHING, IN), 0, 1),
+        ("b, gamma, beta but no w, eval_bn", [None, tb, tg, tbe], True, False, (FRESH, FRESH, FRESH), 0, 0),
+    ]
+    for name, targets, eval_bn, xyz_first, (where_w, where_b, where_gb), acc_w, acc_gb in table:
+        # (the slots of layer 1 of a two-layer stack: the helper must pick entries 4..7)
+        s = LayerSlots(None if targets is None else [None] * 4 + targets, 1, w, eval_bn, xyz_first_layer=xyz_first)
+        gw, gb, gg, gbe = s.grads
+        assert (s.acc_w, s.acc_gb) == (acc_w, acc_gb), name
+        if where_w == IN:
+            assert s.dw_p == tw.data_ptr() and gw is None, name
+        else:
+            assert gw.shape == w.shape and gw.dtype == torch.float32 and s.dw_p == gw.data_ptr() != tw.data_ptr(), name
+        if where_b == IN:
+            assert s.db_p == tb.data_ptr() and gb is None and s.db is None, name
+        elif where_b == NOTHING:
+            assert s.db_p is None and gb is None and s.db is None, name
+        else:
+            assert gb.shape == (cout,) and s.db_p == gb.data_ptr() != tb.data_ptr() and s.db is gb, name
+        if where_gb == IN:
+            assert (s.dgamma_p, s.dbeta_p) == (tg.data_ptr(), tbe.data_ptr()) and gg is None and gbe is None, name
+        else:
+            assert gg.shape == gbe.shape == (cout,) and (s.dgamma_p, s.dbeta_p) == (gg.data_ptr(), gbe.data_ptr()), name
+            assert s.dgamma_p not in (tg.data_ptr(), tbe.data_ptr()) and s.dbeta_p not in (tg.data_ptr(), tbe.data_ptr()), name
