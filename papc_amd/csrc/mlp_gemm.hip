@@ -395,6 +395,11 @@ __global__ __launch_bounds__((1 + WS) * WGM * WGN * 64, WS ? (1 + WS) : WGM * WG
             for (int wn = 0; wn < WN; ++wn) {
                 const int col = n0 + (wgn * WN + wn) * 32 + l31;
                 if (cok[wn]) {
+                    // the statistics of THIS tile are summed from zero and added to the running pair at the end: a workgroup that walks
+                    // many row tiles would otherwise carry one serial fp32 chain over all of them (16 terms per lane and tile), and the
+                    // BatchNorm mean / variance its rounding.  One tile per workgroup: 0 + t, the same bits as before.
+                    const float run1 = s1[wn], run2 = s2[wn];
+                    s1[wn] = 0.f; s2[wn] = 0.f;
                     float dsum = 0.f;                    // scatter epilogue: pending sum of padding duplicates ...
                     int dgrp = -1, djf = -1, dbat = 0;   // ... of group dgrp (first neighbour djf, cloud dbat)
                     if (EPI == EPI_STORE_GMAX) {
@@ -567,6 +572,7 @@ __global__ __launch_bounds__((1 + WS) * WGM * WGN * 64, WS ? (1 + WS) : WGM * WG
                     }
                     if (EPI == EPI_SCATTER && dgrp >= 0 && djf >= 0 && djf < p.sc.N)
                         unsafeAtomicAdd(&p.sc.gf[((int64_t)dbat * p.sc.N + djf) * p.sc.D + col], dsum);
+                    s1[wn] = run1 + s1[wn]; s2[wn] = run2 + s2[wn];
                 }
 #pragma unroll
                 for (int wm = 0; wm < WM; ++wm)
@@ -842,6 +848,19 @@ static void dbg_report(const GemmArgs &p, int amode, int epi, unsigned gx)
         if (dbg_on) dbg_report0(p, AMODE, EPI, gx, a * b);                                                             \
     } while (0)
 
+// which column-tile configuration a problem of gx row tiles and Nout columns runs: 128 (2x2 or 2x4 waves), 64 (<2,2,2,1>) or 32
+// (<4,1,1,1>).  The one rule of the launcher and of papc_mlp_gemm_gmax_ok.
+// few row tiles (group_all layers: M = B*N ~ 4096): 128-wide column tiles would leave most CUs idle, so use
+// 64- (or 32-) wide ones to get >= ~256 workgroups; the A tile is then re-read from L2 by more workgroups
+static int gemm_col_tile(int64_t gx, int Nout)
+{
+    if (Nout <= 32) return 32;
+    if (Nout <= 64) return 64;
+    const int minwg = knob(KNOB_GEMM_MINWG);
+    if (gx * cdiv(Nout, 128) >= minwg || gx * cdiv(Nout, 64) >= 1024) return 128;
+    return gx * cdiv(Nout, 64) >= minwg ? 64 : 32;
+}
+
 template <int AMODE, int EPI, bool VEC, bool TL>
 static int launch_gemm_v(const GemmArgs &p_in, hipStream_t st)
 {
@@ -854,23 +873,12 @@ static int launch_gemm_v(const GemmArgs &p_in, hipStream_t st)
     }
     const unsigned gx = (unsigned)gemm_parts(p.M);
     p.parts = (int)gx;
-    // few row tiles (group_all layers: M = B*N ~ 4096): 128-wide column tiles would leave most CUs idle, so use
-    // 64- (or 32-) wide ones to get >= ~256 workgroups; the A tile is then re-read from L2 by more workgroups
-    const int64_t wg128 = (int64_t)gx * cdiv(p.Nout, 128);
     // few row tiles also means ONE tile per workgroup: the k loop is a serial chain of load -> transform -> MFMA stages with nothing
     // to overlap it, so those problems take 32-wide k stages (half as many): kb2
     const int kb_env = knob(KNOB_GEMM_KB);
     const bool kb2 = !TL && (kb_env == 2 || (kb_env != 1 && gx <= 64));   // PAPC_GEMM_KB=1: never, =2: always (experiment)
-    const int minwg = knob(KNOB_GEMM_MINWG);
-    if (p.Nout > 64 && wg128 < minwg && (int64_t)gx * cdiv(p.Nout, 64) < 1024) {
-        if ((int64_t)gx * cdiv(p.Nout, 64) >= minwg || p.Nout <= 64) {
-            dim3 grid(gx, (unsigned)cdiv(p.Nout, 64));
-            GEMM_LAUNCH(2, 2, 2, 1);
-        } else {
-            dim3 grid(gx, (unsigned)cdiv(p.Nout, 32));
-            GEMM_LAUNCH(4, 1, 1, 1);
-        }
-    } else if (p.Nout > 64) {
+    const int tile_n = gemm_col_tile(gx, p.Nout);
+    if (tile_n == 128) {
         dim3 grid(gx, (unsigned)cdiv(p.Nout, 128));
         if (!gemm_f32_exact() && gemm_ws() == 3)        // 4 consumer + 12 producer waves on the same 128x128 tile
         {
@@ -885,11 +893,11 @@ static int launch_gemm_v(const GemmArgs &p_in, hipStream_t st)
         }
         else
             GEMM_LAUNCH(2, 2, 2, 2);
-    } else if (p.Nout > 32) {
-        dim3 grid(gx, 1);
+    } else if (tile_n == 64) {
+        dim3 grid(gx, (unsigned)cdiv(p.Nout, 64));
         GEMM_LAUNCH(2, 2, 2, 1);
     } else {
-        dim3 grid(gx, 1);
+        dim3 grid(gx, (unsigned)cdiv(p.Nout, 32));
         GEMM_LAUNCH(4, 1, 1, 1);
     }
     return check_launch("mlp gemm");
@@ -995,9 +1003,7 @@ int papc_mlp_gemm_gmax_ok(int64_t M, int Cout, int K)
     // with few row tiles the launcher switches to the 4x1 narrow configuration (see launch_gemm_v), which is excluded too
     if (!(K == 32 || K == 64 || K == 128) || M % 128 != 0 || Cout <= 32 || Cout % 32 != 0) return 0;  // (whole 32-column wave tiles: the K = 128 exchange has a barrier)
     if (K == 128 && !(Cout == 64 || Cout % 128 == 0)) return 0;   // every wave of a column block must take part in the exchange
-    const int64_t gx = gemm_parts(M);
-    if (Cout > 64 && gx * cdiv(Cout, 128) < 192 && gx * cdiv(Cout, 64) < 1024 && !(gx * cdiv(Cout, 64) >= 192)) return 0;
-    return 1;
+    return gemm_col_tile(gemm_parts(M), Cout) != 32;
 }
 
 int papc_mlp_gemm_f32(int a_mode, const float *x, int64_t ldx, const papc_group_src *grp,

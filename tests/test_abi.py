@@ -44,6 +44,25 @@ def test_argument_validation_without_gpu():
         _lib.check(-1, "x")
 
 
+def test_gmax_ok_follows_the_launchers_tile_width_knob():
+    """papc_mlp_gemm_gmax_ok and launch_gemm_v share one column-tile rule (mlp_gemm.hip::gemm_col_tile), PAPC_GEMM_MINWG included: a layer
+    the raised knob sends to the 32-column <4,1,1,1> configuration (no fused group max there) is refused, and with the knob lowered the
+    128-column tile -- and with it the fused epilogue -- is allowed on a handful of row tiles."""
+    lib = _lib.load()
+    old = ctypes.c_int(0)
+    _lib.check(lib.papc_knob_get(b"PAPC_GEMM_MINWG", ctypes.byref(old)), "papc_knob_get")
+    assert old.value == 192
+    try:
+        _lib.check(lib.papc_knob_set(b"PAPC_GEMM_MINWG", 4096), "papc_knob_set")
+        assert lib.papc_mlp_gemm_gmax_ok(32768, 128, 64) == 0
+        assert lib.papc_mlp_gemm_gmax_ok(32768, 128, 128) == 0
+        _lib.check(lib.papc_knob_set(b"PAPC_GEMM_MINWG", 1), "papc_knob_set")
+        assert lib.papc_mlp_gemm_gmax_ok(1024, 128, 64) == 1
+    finally:
+        _lib.check(lib.papc_knob_set(b"PAPC_GEMM_MINWG", old.value), "papc_knob_set")
+    assert lib.papc_mlp_gemm_gmax_ok(32768, 128, 64) == 1 and lib.papc_mlp_gemm_gmax_ok(1024, 128, 64) == 0      # the default rule, unchanged
+
+
 def test_no_cpu_fallback():
     import torch
     from papc_amd import functional as F

@@ -30,6 +30,42 @@ def test_fps_literal_c_and_torch_agree():
     assert np.array_equal(t.numpy().astype(np.int32), c)
 
 
+def test_fps_lattice_is_exact_in_fp32_and_the_oracle_is_deterministic_on_it():
+    """The tie-breaking input of tests/test_gpu_geometry.py: on the shuffled 26^3 lattice (spacing 1/8) fp32 squared distances equal the
+    float64 ones bit for bit in either summation order, and the two formulations of the oracle loop (numpy step by step, C restatement) pick
+    identical indices on the N = 16 384 prefix for both initial distances.  How often the maximum is shared (this fixed data): in every
+    iteration with init_dist = 1.0 (the running distances are clipped to exactly 1.0), in 20 of 62 with 1e10 -- only the first-maximum rule
+    decides those."""
+    from tests.util import fps_lattice
+    B, N, npoint = 2, 16384, 32
+    full = fps_lattice(B, 26)
+    assert full.shape == (B, 26 ** 3, 3) and full.dtype == np.float32
+    assert np.array_equal(full * 8, np.round(full * 8)) and full.min() == 0.0 and full.max() == 3.125
+    assert len(np.unique(full[0], axis=0)) == 26 ** 3           # a permutation of distinct points
+    xyz = np.ascontiguousarray(full[:, :N])
+    st = np.array([5, N - 1], np.int64)
+    for init in (1e10, 1.0):
+        lit = R.farthest_point_sample_literal(xyz, npoint, st, init)
+        c = R.farthest_point_sample(xyz, npoint, st, init)
+        assert np.array_equal(lit.astype(np.int32), c), init
+        assert np.array_equal(c, R.farthest_point_sample(xyz, npoint, st, init))
+        # replay the C oracle's picks: exact distances, and a maximum that several points share in (nearly) every iteration
+        dist = np.full((B, N), init, np.float32)
+        tied = 0
+        for i in range(npoint):
+            cen = xyz[np.arange(B), c[:, i]][:, None, :]
+            d = (xyz - cen) ** 2
+            d32 = (d[..., 0] + d[..., 1]) + d[..., 2]
+            d64 = ((xyz.astype(np.float64) - cen.astype(np.float64)) ** 2).sum(-1)
+            assert d32.dtype == np.float32 and np.array_equal(d32.astype(np.float64), d64)
+            assert np.array_equal((d[..., 2] + d[..., 1]) + d[..., 0], d32)
+            dist = np.minimum(dist, d32)
+            if i + 1 < npoint:
+                assert np.array_equal(np.argmax(dist, -1), c[:, i + 1])
+                tied += int(((dist == dist.max(-1, keepdims=True)).sum(-1) > 1).sum())
+        assert tied == B * (npoint - 1) if init == 1.0 else tied >= 10, (init, tied)
+
+
 def test_fps_init_one_clips_and_ties_take_lowest_index():
     # two far clusters: every point farther than 1 from the start keeps distance 1.0 -> argmax = lowest such index
     xyz = np.zeros((1, 6, 3), np.float32)

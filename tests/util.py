@@ -116,3 +116,12 @@ def kernel_decisions(out):
             m = (c[2].double() * y.double() + c[3].double()) > 0
             masks.append(m if rowmap is None else m[rowmap])
     return argmax, alive, masks
+
+
+def fps_lattice(B, seed, side=26, spacing=0.125):
+    """[B, side^3, 3] float32: per cloud its own shuffle of a cubic lattice.  Coordinates are small multiples of 1/8 and every squared distance
+    a multiple of 1/64 far below 2^24 / 64, so fp32 computes them EXACTLY in any order: farthest-point sampling on a prefix of such a cloud
+    ties among many points in every iteration, and only the first-maximum rule decides (tests/test_oracle.py checks both claims)."""
+    rng = np.random.default_rng(seed)
+    g = np.stack(np.meshgrid(*[np.arange(side)] * 3, indexing="ij"), -1).reshape(-1, 3).astype(np.float32) * np.float32(spacing)
+    return np.stack([g[rng.permutation(len(g))] for _ in range(B)])
