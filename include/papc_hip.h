@@ -725,6 +725,37 @@ int papc_kdconv_bwd_f32(const float *gout, const float *out, const uint8_t *win,
                         const float *w, int B, int dim, int Cin, int F, float *dx, int64_t ldd, float *dw, float *dbias, int accumulate, void *workspace,
                         size_t workspace_bytes, papc_stream_t stream);
 
+/* One down level of the KDUNet part segmenter (PAPC/models/segment/kdunet/kdunet.py:51-61): Conv1D(Cin, 3F, 1), BatchNorm over all 3F channels,
+ * ReLU, the kd-tree select and the pair max of papc_kdconv_* (same layouts, same index rule, same winner byte) -- computing only the selected
+ * third of the conv (csrc/kdbn.hip).  The conv is linear in its rows, so the batch statistics of all 3F channels follow from the mean xm [Cin]
+ * and the centred second moment C [Cin, Cin] of x:  mu_c = w_c . xm + bias_c,  var_c = w_c^T C w_c / M (biased, M = B * dim); the backward's
+ * dense BatchNorm terms collapse onto C the same way.  [B * dim, 3F] is never formed, in either direction.
+ *   papc_kdbn_ok         != 0 where the kernels take the shape: dim even and >= 2, Cin = 3 or a multiple of 32 up to 512, F a multiple of 32
+ *                        up to 1024.  The calls below return PAPC_E_UNSUPPORTED elsewhere, naming the value.
+ *   papc_kdbn_fwd_f32    training != 0: the batch statistics (workspace: papc_kdbn_fwd_workspace bytes, 16-byte aligned), written to
+ *                        mean [Cin], tmat [3F, Cin] (= W C) and stats [4, 3F] = (w . xm | 1 / sqrt(var + eps) | mu | var); running_mean /
+ *                        running_var (may be NULL) <- momentum * running + (1 - momentum) * batch, the biased variance.
+ *                        training == 0: stats from the running statistics and the bias; mean, tmat and the workspace are not touched.
+ *                        Then out, win and zhat [B * dim / 2, F]: the winner's normalised value (w . x - stats[0]) * stats[1];
+ *                        out = relu(gamma * zhat + beta) of the winner.
+ *   papc_kdbn_bwd_f32    from gout and the forward's out, win, zhat, mean, tmat, stats: dx (NULL: skipped; every point receives a
+ *                        gradient), dw [3F, Cin], dgamma, dbeta [3F], added to what they hold when accumulate != 0; dbias [3F] (may be NULL)
+ *                        is set to exact zeros in train mode (nothing is added under accumulate: the bias cancels in the norm) and receives
+ *                        its gradient in eval mode.  training must be the forward's.  Workspace: papc_kdbn_bwd_workspace bytes.
+ * Per-chunk partial sums folded in chunk order: no atomics, bit-reproducible.  B * dim <= 2^28; Cin >= 32: x / w / gout / out / mean 16-byte
+ * aligned, ldx a multiple of 4.  Products: bf16x3 on v_mfma_f32_32x32x16_bf16, Cin = 3: fmaf chains. */
+int papc_kdbn_ok(int dim, int Cin, int F);
+size_t papc_kdbn_fwd_workspace(int B, int dim, int Cin, int F);
+int papc_kdbn_fwd_f32(const float *x, int64_t ldx, const int32_t *sel, int64_t sel_stride, const float *w, const float *bias, const float *gamma,
+                      const float *beta, float *running_mean, float *running_var, int B, int dim, int Cin, int F, float eps, float momentum, int training,
+                      float *out, uint8_t *win, float *zhat, float *mean, float *tmat, float *stats, void *workspace, size_t workspace_bytes,
+                      papc_stream_t stream);
+size_t papc_kdbn_bwd_workspace(int B, int dim, int Cin, int F);
+int papc_kdbn_bwd_f32(const float *gout, const float *out, const uint8_t *win, const float *zhat, const float *x, int64_t ldx, const int32_t *sel,
+                      int64_t sel_stride, const float *w, const float *gamma, const float *mean, const float *tmat, const float *stats, int B, int dim,
+                      int Cin, int F, int training, float *dx, int64_t ldd, float *dw, float *dbias, float *dgamma, float *dbeta, int accumulate,
+                      void *workspace, size_t workspace_bytes, papc_stream_t stream);
+
 /* Axis-aligned bitmask NMS: nms_gpu of pointpillars/libs/ops/non_max_suppression/nms_gpu.py:130-164 (CUDA twin
  * libs/ops/cc/nms/nms_kernel.cu.cc:38-157), all on the device.  dets [N,5] = (x1, y1, x2, y2, score) fp32, N <= 65536.
  * keep [N] int32 receives the ORIGINAL indices of the kept boxes in descending-score order (ties: higher index first, the

@@ -156,6 +156,13 @@ SIGNATURES = {
     "papc_kdconv_fwd_f32": (c_i, [c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
     "papc_kdconv_bwd_workspace": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
     "papc_kdconv_bwd_f32": (c_i, [c_p, c_p, c_p, c_p, c_l, c_p, c_l, c_p, c_i, c_i, c_i, c_i, c_p, c_l, c_p, c_p, c_i, c_p, ctypes.c_size_t, c_p]),
+    "papc_kdbn_ok": (c_i, [c_i, c_i, c_i]),
+    "papc_kdbn_fwd_workspace": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
+    "papc_kdbn_fwd_f32": (c_i, [c_p, c_l, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                ctypes.c_size_t, c_p]),
+    "papc_kdbn_bwd_workspace": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
+    "papc_kdbn_bwd_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_l, c_p, c_p, c_p, c_p, c_i,
+                                c_p, ctypes.c_size_t, c_p]),
     "papc_nms_workspace": (ctypes.c_size_t, [c_i]),
     "papc_nms_f32": (c_i, [c_p, c_i, c_f, c_p, c_p, c_p, ctypes.c_size_t, c_p]),
     "papc_lingather_parts": (c_i, [c_l]),

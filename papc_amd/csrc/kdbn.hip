@@ -1,0 +1,823 @@
+// kdbn.hip -- one down level of the KDUNet part segmenter, for gfx950: 1x1 conv to 3F channels, BatchNorm over all 3F channels, ReLU, the
+// kd-tree select, the max over point pairs.
+//
+// Reference: PAPC/models/segment/kdunet/kdunet.py:51-61 (ConvBNReLU :20-39)
+//     x = relu(batch_norm(conv(x)));  x = reshape(x, (-1, F, 3, dim));  x = reshape(x, (-1, F, 3 * dim));
+//     x = index_select(x, axis=2, index=sel + 3 * arange(dim));  x = max(reshape(x, (-1, F, dim / 2, 2)), axis=-1)
+// The select is kdconv.hip's (kdsel.h): pre-pool row n takes channel 3f + k at source point p.  The BatchNorm statistics run over EVERY point
+// and every one of the 3F channels, but the conv is linear in its input rows, so they follow from the moments of the Cin-wide rows
+// x [M = B dim, Cin]:  xm = mean_n x[n],  C = sum_n (x[n] - xm)(x[n] - xm)^T,  T = W C  [3F, Cin]:
+//     mu_c = w_c . xm + b_c     var_c = max(T_c . w_c / M, 0)     rstd_c = 1 / sqrt(var_c + eps)     r_c = gamma_c rstd_c
+//     zhat_c[n] = (w_c . x[n] - w_c . xm) rstd_c     a = gamma zhat + beta     y = relu(a)     out[m, f] = max(y[2m], y[2m + 1])
+// (the conv bias cancels out of a; it enters the running mean only).  Only the selected third of the conv is computed and the [M, 3F]
+// activations are never formed, in either direction.  With g[n, c] = gout where (n, c) was selected, won its pair and out > 0, else 0:
+//     dbeta_c = sum_n g_c[n]      dgamma_c = sum_n g_c[n] zhat_c[n]      S_c = sum_n g_c[n] x[p(n)]
+//     dW_c = r_c (S_c - dbeta_c xm - (dgamma_c rstd_c / M) T_c)          d bias = 0
+//     dX[n] = sum_c r_c g_c[n] w_c - v - (x[n] - xm) A       v = sum_c (r_c dbeta_c / M) w_c      A = W^T diag(r_c dgamma_c rstd_c / M) W
+//
+//   moments   kb_colsum_kernel: column sums of chunks of 256 rows; kb_mean_kernel folds them in chunk order (fold.h, in-order) -> xm.
+//             kb_gram_kernel: the CENTRED second moment of a chunk (two passes over x: no cancellation), a wave per 32 x 32 block of C;
+//             folded in chunk order by papc_reduce_partials_f32.  kb_t_kernel: T = W C (C's two triangles agree to rounding; the B operand
+//             reads C by rows).  kb_finalize_kernel: a wave per channel, double sums -> zoff = w . xm, rstd, mu, var; running statistics
+//             momentum * running + (1 - momentum) * batch, the biased variance (models._bn1d, bn_ops.hip).
+//             Eval mode: kb_eval_kernel takes zoff = running_mean - bias, rstd from running_var; the forward kernel is the same.
+//   forward   kb_fwd_kernel: kd_fwd_kernel's wave layout; epilogue zhat = (acc - zoff) rstd, a = gamma zhat + beta, ReLU, pair max.  Writes
+//             out, the winner byte and the winner's zhat (the backward's dgamma needs it; it is never recovered by dividing by gamma).
+//   backward  kb_dw_kernel: kd_dw_kernel with a third sum -> per chunk S [3F, Cin], dbeta [3F], dgamma [3F]; folded in chunk order by
+//             papc_reduce_partials2_f32.  kb_dwfin_kernel: dW, dgamma, dbeta (d bias = exact zeros, nothing under accumulate) and the
+//             per-channel coefficients r, r dbeta / M, r dgamma rstd / M.  kb_a_kernel: A and v, a wave per 32 x 32 block and slice of the 3F
+//             channels, the slices folded in slice order.  kb_dx_kernel: kd_dx_kernel with r g in place of dy, then Cin more k steps (x - xm) (-A), minus v.
+//             No float atomics, every sum in a fixed order: two runs are bit-identical.  In eval mode the norm is a fixed affine map:
+//             dW_c = r_c S_c, d bias_c = r_c dbeta_c, dX is the sparse term alone.
+// Products: bf16x3.h on v_mfma_f32_32x32x16_bf16 (fp32 accuracy, fp32 accumulation) for Cin >= 32; the Cin = 3 first level runs fmaf chains
+// on the vector unit (the *3_kernel twins).  Plain C++ loads and stores only.
+#include "bf16x3.h"
+#include "fold.h"
+#include "kdsel.h"
+
+namespace papc {
+
+constexpr int KB_T = 256;        // threads of every kernel here (4 waves)
+constexpr int KB_CH = 128;       // rows per S chunk (MFMA kernel)
+constexpr int KB_CH3 = 256;      // rows per S chunk (Cin = 3 kernel)
+constexpr int KB_MCH = 256;      // rows per moments chunk
+
+// the 16-wide k step both operands of which are 8 consecutive floats per lane
+__device__ __forceinline__ floatx16 kb_step(const float (&av)[8], const float (&bv)[8], floatx16 acc)
+{
+    bf16x8 ap[3], bp[3];
+    split8(av, ap);
+    split8(bv, bp);
+    return mfma_bf16x3(ap, bp, acc);
+}
+
+__device__ __forceinline__ void kb_ld8(const float *p, float (&v)[8])
+{
+    const float4 a = kd_ld4(p), b = kd_ld4(p + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+
+// ---- moments ------------------------------------------------------------------------------------------------------------------------
+// chunk t (blockIdx.x) = rows 256 t .. + 255; workgroup = 16 columns (blockIdx.y) x 16 slices of 16 rows, each summed in row order, the slices
+// added in slice order: part[t * Cin + c]
+__global__ __launch_bounds__(KB_T) void kb_colsum_kernel(const float *__restrict__ x, int64_t ldx, int M, int Cin, float *__restrict__ part)
+{
+    __shared__ float red[16][16];
+    const int cl = threadIdx.x & 15, sl = threadIdx.x >> 4;
+    const int c = blockIdx.y * 16 + cl;
+    const int r0 = blockIdx.x * KB_MCH + sl * (KB_MCH / 16), r1 = min(r0 + KB_MCH / 16, M);
+    float s = 0.f;
+    if (c < Cin)
+        for (int m = r0; m < r1; ++m) s += x[(int64_t)m * ldx + c];
+    red[sl][cl] = s;
+    __syncthreads();
+    if (sl != 0 || c >= Cin) return;
+#pragma unroll
+    for (int g = 1; g < 16; ++g) s += red[g][cl];
+    part[(int64_t)blockIdx.x * Cin + c] = s;
+}
+
+__global__ __launch_bounds__(KB_T) void kb_mean_kernel(const float *__restrict__ part, int T, int M, int Cin, float *__restrict__ mean)
+{
+    const int c = blockIdx.x * KB_T + threadIdx.x;
+    if (c >= Cin) return;
+    mean[c] = fold_in_order<8, FOLD_FROM_ZERO, float>(part, Cin, T, c) / (float)M;
+}
+
+// wave = block (cb1, cb2) of the chunk's centred second moment: A[row r = c1][n] = x[n][32 cb1 + r] - xm, B[n][col r] = x[n][32 cb2 + r] - xm
+__global__ __launch_bounds__(KB_T) void kb_gram_kernel(const float *__restrict__ x, int64_t ldx, const float *__restrict__ mean, int M, int Cin,
+                                                       float *__restrict__ part)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    const int ncb = Cin >> 5, id = blockIdx.y * 4 + wv;
+    if (id >= ncb * ncb) return;
+    const int cb1 = id / ncb, cb2 = id - cb1 * ncb;
+    const int c1 = cb1 * 32 + r, c2 = cb2 * 32 + r;
+    const float m1 = mean[c1], m2 = mean[c2];
+    const int r0 = blockIdx.x * KB_MCH;
+    floatx16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    for (int ks = 0; ks < KB_MCH / 16; ++ks) {
+        const int mb = r0 + ks * 16 + 8 * h;
+        if (r0 + ks * 16 >= M) break;                               // (wave-uniform)
+        float av[8], bv[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const bool in = mb + j < M;
+            const float *xr = x + (int64_t)(in ? mb + j : 0) * ldx;
+            av[j] = in ? xr[c1] - m1 : 0.f;
+            bv[j] = in ? xr[c2] - m2 : 0.f;
+        }
+        acc = kb_step(av, bv, acc);
+    }
+    float *pt = part + (int64_t)blockIdx.x * Cin * Cin;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) pt[(int64_t)(cb1 * 32 + (i & 3) + 8 * (i >> 2) + 4 * h) * Cin + c2] = acc[i];
+}
+
+// Cin = 3: workgroup = the 9 elements (c1, c2) of the chunk's centred second moment x 16 slices of 16 rows, the slices added in slice order
+__global__ __launch_bounds__(KB_T) void kb_gram3_kernel(const float *__restrict__ x, int64_t ldx, const float *__restrict__ mean, int M,
+                                                        float *__restrict__ part)
+{
+    __shared__ float red[16][16];
+    const int e = threadIdx.x & 15, sl = threadIdx.x >> 4;
+    const int c1 = min(e / 3, 2), c2 = e % 3;
+    const float m1 = mean[c1], m2 = mean[c2];
+    const int r0 = blockIdx.x * KB_MCH + sl * (KB_MCH / 16), r1 = min(r0 + KB_MCH / 16, M);
+    float s = 0.f;
+    for (int m = r0; m < r1; ++m) {
+        const float *xr = x + (int64_t)m * ldx;
+        s = fmaf(xr[c1] - m1, xr[c2] - m2, s);
+    }
+    red[sl][e] = s;
+    __syncthreads();
+    if (sl != 0 || e >= 9) return;
+#pragma unroll
+    for (int g = 1; g < 16; ++g) s += red[g][e];
+    part[(int64_t)blockIdx.x * 9 + e] = s;
+}
+
+// T = W C.  wave: channels 32 ob .. + 31 (blockIdx.x), columns 32 cb .. + 31: A[row r][c] = W[32 ob + r][c], B[c][col r] = C[32 cb + r][c]
+__global__ __launch_bounds__(KB_T) void kb_t_kernel(const float *__restrict__ w, const float *__restrict__ cm, int Cin, float *__restrict__ tm)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    const int cb = blockIdx.y * 4 + wv;
+    if (cb * 32 >= Cin) return;
+    const int o0 = blockIdx.x * 32;
+    const float *wr = w + (int64_t)(o0 + r) * Cin + 8 * h, *cr = cm + (int64_t)(cb * 32 + r) * Cin + 8 * h;
+    floatx16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    for (int c0 = 0; c0 < Cin; c0 += 16) {
+        float av[8], bv[8];
+        kb_ld8(wr + c0, av);
+        kb_ld8(cr + c0, bv);
+        acc = kb_step(av, bv, acc);
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) tm[(int64_t)(o0 + (i & 3) + 8 * (i >> 2) + 4 * h) * Cin + cb * 32 + r] = acc[i];
+}
+
+__global__ __launch_bounds__(KB_T) void kb_t3_kernel(const float *__restrict__ w, const float *__restrict__ cm, int n_ch, float *__restrict__ tm)
+{
+    const int o = blockIdx.x * KB_T + threadIdx.x;
+    if (o >= n_ch) return;
+    const float w0 = w[3 * o], w1 = w[3 * o + 1], w2 = w[3 * o + 2];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) tm[3 * o + c] = fmaf(w2, cm[6 + c], fmaf(w1, cm[3 + c], w0 * cm[c]));
+}
+
+// one wave per channel o: zoff = w_o . xm, var = T_o . w_o / M in double; stats = [zoff | rstd | mu | var] x [n_ch]
+__global__ __launch_bounds__(64) void kb_finalize_kernel(const float *__restrict__ w, const float *__restrict__ bias, const float *__restrict__ mean,
+                                                         const float *__restrict__ tm, int M, int Cin, int n_ch, float eps, float momentum,
+                                                         float *__restrict__ stats, float *rmean, float *rvar)
+{
+    const int o = blockIdx.x, tl = threadIdx.x;
+    double s1 = 0.0, s2 = 0.0;
+    for (int c = tl; c < Cin; c += 64) {
+        const double wv = (double)w[(int64_t)o * Cin + c];
+        s1 += wv * (double)mean[c];
+        s2 += wv * (double)tm[(int64_t)o * Cin + c];
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {                            // (a butterfly: every lane ends with the same sum, in a fixed order)
+        s1 += __shfl_xor(s1, d);
+        s2 += __shfl_xor(s2, d);
+    }
+    if (tl == 0) {
+        double var = s2 / (double)M;                               // the biased variance (paddle BatchNorm training)
+        if (!(var > 0.0)) var = var != var ? var : 0.0;
+        const float mu = (float)(s1 + (bias ? (double)bias[o] : 0.0));
+        stats[o] = (float)s1;
+        stats[n_ch + o] = (float)(1.0 / sqrt(var + (double)eps));
+        stats[2 * n_ch + o] = mu;
+        stats[3 * n_ch + o] = (float)var;
+        if (rmean) rmean[o] = momentum * rmean[o] + (1.f - momentum) * mu;   // paddle: momentum weighs the running value
+        if (rvar) rvar[o] = momentum * rvar[o] + (1.f - momentum) * (float)var;
+    }
+}
+
+__global__ __launch_bounds__(KB_T) void kb_eval_kernel(const float *__restrict__ bias, const float *__restrict__ rmean, const float *__restrict__ rvar,
+                                                       int n_ch, float eps, float *__restrict__ stats)
+{
+    const int o = blockIdx.x * KB_T + threadIdx.x;
+    if (o >= n_ch) return;
+    const float mu = rmean[o], var = rvar[o];
+    stats[o] = mu - (bias ? bias[o] : 0.f);
+    stats[n_ch + o] = (float)(1.0 / sqrt((double)var + (double)eps));
+    stats[2 * n_ch + o] = mu;
+    stats[3 * n_ch + o] = var;
+}
+
+// ---- forward ------------------------------------------------------------------------------------------------------------------------
+struct KbChan { float zoff, rstd, gamma, beta; };
+
+__device__ __forceinline__ KbChan kb_chan(const float *__restrict__ stats, const float *__restrict__ gamma, const float *__restrict__ beta, int n_ch, int o)
+{
+    return KbChan{stats[o], stats[n_ch + o], gamma[o], beta[o]};
+}
+
+// acc = w . x (no bias) -> zhat, a
+__device__ __forceinline__ void kb_affine(float acc, const KbChan &c, float &z, float &a)
+{
+    z = (acc - c.zoff) * c.rstd;
+    a = c.gamma * z + c.beta;
+}
+
+__device__ __forceinline__ void kb_store_pair(float z0, float a0, float z1, float a1, float *__restrict__ out, unsigned char *__restrict__ win,
+                                              float *__restrict__ zh, int64_t at)
+{
+    const float y0 = relu_np(a0), y1 = relu_np(a1);
+    const bool w1 = y1 > y0 || (y1 != y1 && y0 == y0);     // the first row on an exact tie; a NaN goes through, as the source's max does
+    out[at] = w1 ? y1 : y0;
+    win[at] = w1 ? 1 : 0;
+    zh[at] = w1 ? z1 : z0;
+}
+
+// wave: rows m0 .. m0 + 31 (blockIdx.x), features 32 fb .. + 31 (fb = 4 blockIdx.y + wave): kd_fwd_kernel's layout
+__global__ __launch_bounds__(KB_T) void kb_fwd_kernel(const float *__restrict__ x, int64_t ldx, const int *__restrict__ sel, int64_t ss,
+                                                      const float *__restrict__ w, const float *__restrict__ stats, const float *__restrict__ gamma,
+                                                      const float *__restrict__ beta, int M, int dim, int Cin, int F, float *__restrict__ out,
+                                                      unsigned char *__restrict__ win, float *__restrict__ zh)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    const int fb = blockIdx.y * 4 + wv;
+    if (fb * 32 >= F) return;
+    const int m0 = blockIdx.x * 32;
+    const unsigned info = kd_row_info(m0 + r, M, dim, sel, ss);
+    const int k = (int)(info >> 30);
+    const float *xr = x + (int64_t)(info & KD_ROW) * ldx + 8 * h;
+    const int f = fb * 32 + r;
+    floatx16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    for (int q = 0; q < 3; ++q) {
+        if (__ballot(k == q) == 0) continue;            // (wave-uniform)
+        const bool mine = k == q;
+        const float *wr = w + (int64_t)(3 * f + q) * Cin + 8 * h;
+        for (int c1 = 0; c1 < Cin; c1 += 32)           // (Cin is a multiple of 32: two k steps' loads in flight)
+#pragma unroll
+        for (int c0 = c1; c0 < c1 + 32; c0 += 16) {
+            float av[8], bv[8];
+            if (mine) kb_ld8(xr + c0, av);
+            else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) av[j] = 0.f;
+            }
+            kb_ld8(wr + c0, bv);
+            acc = kb_step(av, bv, acc);
+        }
+    }
+    const KbChan ch[3] = {kb_chan(stats, gamma, beta, 3 * F, 3 * f), kb_chan(stats, gamma, beta, 3 * F, 3 * f + 1), kb_chan(stats, gamma, beta, 3 * F, 3 * f + 2)};
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int row = 8 * g + 4 * h + 2 * t;      // lanes 0..31 hold the planes of rows 0..31
+            const int k0 = __shfl(k, row), k1 = __shfl(k, row + 1);
+            const int m = m0 + row;
+            if (m < M) {                                // (M is even: row m + 1 exists)
+                float z0, a0, z1, a1;
+                kb_affine(acc[4 * g + 2 * t], k0 == 0 ? ch[0] : (k0 == 1 ? ch[1] : ch[2]), z0, a0);
+                kb_affine(acc[4 * g + 2 * t + 1], k1 == 0 ? ch[0] : (k1 == 1 ? ch[1] : ch[2]), z1, a1);
+                kb_store_pair(z0, a0, z1, a1, out, win, zh, (int64_t)(m >> 1) * F + f);
+            }
+        }
+}
+
+// Cin = 3: thread = (output row, feature)
+__global__ __launch_bounds__(KB_T) void kb_fwd3_kernel(const float *__restrict__ x, int64_t ldx, const int *__restrict__ sel, int64_t ss,
+                                                       const float *__restrict__ w, const float *__restrict__ stats, const float *__restrict__ gamma,
+                                                       const float *__restrict__ beta, int M, int dim, int F, float *__restrict__ out,
+                                                       unsigned char *__restrict__ win, float *__restrict__ zh)
+{
+    const int64_t t = (int64_t)blockIdx.x * KB_T + threadIdx.x;
+    if (t >= (int64_t)(M >> 1) * F) return;
+    const int om = (int)(t / F), f = (int)(t - (int64_t)om * F);
+    float z[2], a[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const unsigned info = kd_row_info(2 * om + e, M, dim, sel, ss);
+        const float *xr = x + (int64_t)(info & KD_ROW) * ldx;
+        const int o = 3 * f + (int)(info >> 30);
+        const float *wr = w + (int64_t)o * 3;
+        const float acc = fmaf(wr[2], xr[2], fmaf(wr[1], xr[1], wr[0] * xr[0]));
+        kb_affine(acc, kb_chan(stats, gamma, beta, 3 * F, o), z[e], a[e]);
+    }
+    kb_store_pair(z[0], a[0], z[1], a[1], out, win, zh, t);
+}
+
+// ---- backward: the sparse sums S, dbeta, dgamma ----------------------------------------------------------------------------------------
+// chunk t (blockIdx.x) = rows 128 t .. + 127; wave = one 32 x 32 block (features 32 fb .. , input channels 32 cb ..) of each of the three
+// planes: kd_dw_kernel's layout.  part + t * pld: S [3F, Cin] of the chunk, then dbeta [3F], then dgamma [3F].
+__global__ __launch_bounds__(KB_T) void kb_dw_kernel(const float *__restrict__ gout, const float *__restrict__ outv, const unsigned char *__restrict__ win,
+                                                     const float *__restrict__ zh, const float *__restrict__ x, int64_t ldx, const int *__restrict__ sel,
+                                                     int64_t ss, int M, int dim, int Cin, int F, float *__restrict__ part, int64_t pld)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    const int ncb = Cin >> 5, id = blockIdx.y * 4 + wv;
+    if (id >= (F >> 5) * ncb) return;
+    const int fb = id / ncb, cb = id - fb * ncb;
+    const int f = fb * 32 + r;
+    const int r0 = blockIdx.x * KB_CH;
+    floatx16 acc[3];
+    float dbs[3] = {0.f, 0.f, 0.f}, dgs[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[q][i] = 0.f;
+    for (int ks = 0; ks < KB_CH / 16; ++ks) {
+        const int mb = r0 + ks * 16;
+        if (mb >= M) break;                                        // (wave-uniform)
+        const unsigned info = kd_row_info(mb + (lane & 15), M, dim, sel, ss);     // the 16 rows of this k step, four times over
+        const int kl = (int)(info >> 30);
+        float dyv[8], zv[8], bv[8];
+        int kj[8];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {                              // rows mb + 8h + 2t, + 1 = pooled row (mb + 8h) / 2 + t
+            const int mr = mb + 8 * h + 2 * t;
+            float g = 0.f, z = 0.f;
+            unsigned wb = 0;
+            if (mr < M) {
+                const int64_t at = (int64_t)(mr >> 1) * F + f;
+                g = outv[at] > 0.f ? gout[at] : 0.f;
+                z = zh[at];
+                wb = win[at];
+            }
+            dyv[2 * t] = wb == 0 ? g : 0.f;
+            dyv[2 * t + 1] = wb == 0 ? 0.f : g;
+            zv[2 * t] = zv[2 * t + 1] = z;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const unsigned inf = (unsigned)__shfl((int)info, 8 * h + j);
+            kj[j] = (int)(inf >> 30);
+            bv[j] = kj[j] < 3 ? x[(int64_t)(inf & KD_ROW) * ldx + cb * 32 + r] : 0.f;
+        }
+        bf16x8 bp[3];
+        split8(bv, bp);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            if (__ballot(kl == q) == 0) continue;
+            float am[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) am[j] = kj[j] == q ? dyv[j] : 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                dbs[q] += am[j];
+                dgs[q] = fmaf(am[j], zv[j], dgs[q]);
+            }
+            bf16x8 ap[3];
+            split8(am, ap);
+            acc[q] = mfma_bf16x3(ap, bp, acc[q]);
+        }
+    }
+    float *pt = part + (int64_t)blockIdx.x * pld;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int fr = fb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+            pt[(int64_t)(3 * fr + q) * Cin + cb * 32 + r] = acc[q][i];
+        }
+        const float tb = dbs[q] + __shfl_xor(dbs[q], 32), tg = dgs[q] + __shfl_xor(dgs[q], 32);     // the two row halves of the lane pair
+        if (cb == 0 && h == 0) {
+            pt[(int64_t)3 * F * Cin + 3 * f + q] = tb;
+            pt[(int64_t)3 * F * Cin + 3 * F + 3 * f + q] = tg;
+        }
+    }
+}
+
+// Cin = 3: chunk t = rows 256 t .. + 255; workgroup = 32 features (blockIdx.y) x 8 slices of the chunk's pooled rows (kd_dw3_kernel's layout).
+__global__ __launch_bounds__(KB_T) void kb_dw3_kernel(const float *__restrict__ gout, const float *__restrict__ outv, const unsigned char *__restrict__ win,
+                                                      const float *__restrict__ zh, const float *__restrict__ x, int64_t ldx, const int *__restrict__ sel,
+                                                      int64_t ss, int M, int dim, int F, float *__restrict__ part, int64_t pld)
+{
+    __shared__ float red[8][15][32];
+    const int fl = threadIdx.x & 31, sl = threadIdx.x >> 5;
+    const int f = blockIdx.y * 32 + fl;
+    const int om0 = blockIdx.x * (KB_CH3 / 2);
+    float a[15];
+#pragma unroll
+    for (int i = 0; i < 15; ++i) a[i] = 0.f;
+    for (int i = sl; i < KB_CH3 / 2; i += 8) {
+        const int om = om0 + i;
+        if (2 * om >= M) break;
+        const int64_t at = (int64_t)om * F + f;
+        const float g = outv[at] > 0.f ? gout[at] : 0.f, z = zh[at];
+        const unsigned info = kd_row_info(2 * om + (win[at] ? 1 : 0), M, dim, sel, ss);
+        const int k = (int)(info >> 30);
+        const float *xr = x + (int64_t)(info & KD_ROW) * ldx;
+        const float x0 = xr[0], x1 = xr[1], x2 = xr[2];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const float d = k == q ? g : 0.f;
+            a[5 * q] = fmaf(d, x0, a[5 * q]);
+            a[5 * q + 1] = fmaf(d, x1, a[5 * q + 1]);
+            a[5 * q + 2] = fmaf(d, x2, a[5 * q + 2]);
+            a[5 * q + 3] += d;
+            a[5 * q + 4] = fmaf(d, z, a[5 * q + 4]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 15; ++i) red[sl][i][fl] = a[i];
+    __syncthreads();
+    if (sl != 0) return;
+    float *pt = part + (int64_t)blockIdx.x * pld;
+#pragma unroll
+    for (int i = 0; i < 15; ++i) {
+        float s = a[i];
+#pragma unroll
+        for (int g = 1; g < 8; ++g) s += red[g][i][fl];
+        const int q = i / 5, c = i - 5 * q;
+        if (c < 3) pt[(int64_t)(3 * f + q) * 3 + c] = s;
+        else pt[(int64_t)3 * F * 3 + (c - 3) * 3 * F + 3 * f + q] = s;
+    }
+}
+
+// thread = element (o, c) of dW; the c = 0 thread of a channel also writes dgamma, dbeta, the zero bias gradient and the coefficients
+// coef = [r | r dbeta / M | r dgamma rstd / M] x [n_ch].  eval: the norm is a fixed affine map.
+__global__ __launch_bounds__(KB_T) void kb_dwfin_kernel(const float *__restrict__ S, const float *__restrict__ dbg, const float *__restrict__ stats,
+                                                        const float *__restrict__ gamma, const float *__restrict__ mean, const float *__restrict__ tm,
+                                                        int M, int Cin, int n_ch, int eval, int accumulate, float *__restrict__ dw,
+                                                        float *__restrict__ dbias, float *__restrict__ dgamma, float *__restrict__ dbeta,
+                                                        float *__restrict__ coef)
+{
+    const int64_t i = (int64_t)blockIdx.x * KB_T + threadIdx.x;
+    if (i >= (int64_t)n_ch * Cin) return;
+    const int o = (int)(i / Cin), c = (int)(i - (int64_t)o * Cin);
+    const float rstd = stats[n_ch + o], r = gamma[o] * rstd, db = dbg[o], dg = dbg[n_ch + o];
+    const float cg = eval ? 0.f : dg * rstd / (float)M;
+    float g = S[i];
+    if (!eval) g = g - db * mean[c] - cg * tm[i];
+    g *= r;
+    dw[i] = accumulate ? dw[i] + g : g;
+    if (c != 0) return;
+    dgamma[o] = accumulate ? dgamma[o] + dg : dg;
+    dbeta[o] = accumulate ? dbeta[o] + db : db;
+    if (dbias) {
+        if (eval) dbias[o] = accumulate ? dbias[o] + r * db : r * db;
+        else if (!accumulate) dbias[o] = 0.f;
+    }
+    coef[o] = r;
+    coef[n_ch + o] = eval ? 0.f : r * db / (float)M;
+    coef[2 * n_ch + o] = r * cg;
+}
+
+// ---- backward: A = W^T diag(e) W and v = W^T d ------------------------------------------------------------------------------------------
+// wave = block (cb1, cb2) of A over the channels of slice blockIdx.y (ks_per k steps of 16 channels), in order: A-operand[row r = c1][o] =
+// e_o W[o][32 cb1 + r], B[o][col r] = W[o][32 cb2 + r]; the cb1 = 0 waves also sum v[32 cb2 + r].  part + slice * (Cin^2 + Cin): [A | v].
+__global__ __launch_bounds__(KB_T) void kb_a_kernel(const float *__restrict__ w, const float *__restrict__ coef, int Cin, int n_ch, int ks_per,
+                                                    float *__restrict__ part)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    const int ncb = Cin >> 5, id = blockIdx.x * 4 + wv;
+    if (id >= ncb * ncb) return;
+    const int cb1 = id / ncb, cb2 = id - cb1 * ncb;
+    const float *d = coef + n_ch, *e = coef + 2 * n_ch;
+    floatx16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    float vs = 0.f;
+    const int o_lo = blockIdx.y * ks_per * 16, o_hi = min(o_lo + ks_per * 16, n_ch);
+    for (int o0 = o_lo; o0 < o_hi; o0 += 16) {                     // (3F is a multiple of 32)
+        float av[8], bv[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int o = o0 + 8 * h + j;
+            const float *wr = w + (int64_t)o * Cin;
+            av[j] = e[o] * wr[cb1 * 32 + r];
+            bv[j] = wr[cb2 * 32 + r];
+            vs = fmaf(d[o], bv[j], vs);
+        }
+        acc = kb_step(av, bv, acc);
+    }
+    float *am = part + (int64_t)blockIdx.y * ((int64_t)Cin * Cin + Cin);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) am[(int64_t)(cb1 * 32 + (i & 3) + 8 * (i >> 2) + 4 * h) * Cin + cb2 * 32 + r] = acc[i];
+    const float tot = vs + __shfl_xor(vs, 32);
+    if (cb1 == 0 && h == 0) am[(int64_t)Cin * Cin + cb2 * 32 + r] = tot;
+}
+
+// Cin = 3: thread t < 9 = element of A, t = 9 .. 11 = element of v
+__global__ __launch_bounds__(64) void kb_a3_kernel(const float *__restrict__ w, const float *__restrict__ coef, int n_ch, float *__restrict__ am,
+                                                   float *__restrict__ v)
+{
+    const int t = threadIdx.x;
+    if (t >= 12) return;
+    const float *d = coef + n_ch, *e = coef + 2 * n_ch;
+    float s = 0.f;
+    if (t < 9) {
+        const int c1 = t / 3, c2 = t - 3 * c1;
+        for (int o = 0; o < n_ch; ++o) s = fmaf(e[o] * w[3 * o + c1], w[3 * o + c2], s);
+        am[t] = s;
+    } else {
+        for (int o = 0; o < n_ch; ++o) s = fmaf(d[o], w[3 * o + t - 9], s);
+        v[t - 9] = s;
+    }
+}
+
+// ---- backward: dX -------------------------------------------------------------------------------------------------------------------
+// wave: source rows m0 .. m0 + 31, input channels 32 cb .. + 31 (kd_dx_kernel's layout).  A[row r][f] = r_c g[row fed by r through plane q][f],
+// B[f][col r] = W[3f + q][32 cb + r]; dense: A[row r][c] = x[m0 + r][c] - xm[c], B[c][col r] = -A[32 cb + r][c] (A's triangles agree to
+// rounding), and v is subtracted in the epilogue.
+__global__ __launch_bounds__(KB_T) void kb_dx_kernel(const float *__restrict__ gout, const float *__restrict__ outv, const unsigned char *__restrict__ win,
+                                                     const int *__restrict__ sel, int64_t ss, const float *__restrict__ w, const float *__restrict__ coef,
+                                                     const float *__restrict__ x, int64_t ldx, const float *__restrict__ mean, const float *__restrict__ am,
+                                                     const float *__restrict__ v, int dense, int M, int dim, int Cin, int F, float *__restrict__ dx,
+                                                     int64_t ldd)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    const int cb = blockIdx.y * 4 + wv;
+    if (cb * 32 >= Cin) return;
+    const int m0 = blockIdx.x * 32, m = m0 + r;
+    const bool live = m < M;
+    const int b = live ? m / dim : 0, p = live ? m - b * dim : 0;
+    floatx16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    for (int q = 0; q < 3; ++q) {
+        int n = 0;
+        const bool vq = live && kd_fed_row(b, p, q, dim, sel, ss, n);
+        if (__ballot(vq) == 0) continue;
+        const int64_t at = (((int64_t)b * dim + n) >> 1) * F + 8 * h;      // (b dim is even)
+        const unsigned par = (unsigned)(n & 1);
+        const float *wq = w + (int64_t)(3 * 8 * h + q) * Cin + cb * 32 + r;
+        const float *rq = coef + 3 * 8 * h + q;
+        for (int f1 = 0; f1 < F; f1 += 32)             // (F is a multiple of 32: two k steps' loads in flight)
+#pragma unroll
+        for (int f0 = f1; f0 < f1 + 32; f0 += 16) {
+            float av[8], bv[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) bv[j] = wq[(int64_t)3 * (f0 + j) * Cin];
+            if (vq) {
+                float g[8], o[8];
+                kb_ld8(gout + at + f0, g);
+                kb_ld8(outv + at + f0, o);
+                const uint2 wb = *reinterpret_cast<const uint2 *>(win + at + f0);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const unsigned wj = ((j < 4 ? wb.x : wb.y) >> (8 * (j & 3))) & 0xffu;
+                    av[j] = (o[j] > 0.f && wj == par) ? g[j] * rq[3 * (f0 + j)] : 0.f;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) av[j] = 0.f;
+            }
+            acc = kb_step(av, bv, acc);
+        }
+    }
+    float vc = 0.f;
+    if (dense) {
+        const float *xr = x + (int64_t)(live ? m : 0) * ldx + 8 * h, *ar = am + (int64_t)(cb * 32 + r) * Cin + 8 * h, *mr = mean + 8 * h;
+        for (int c0 = 0; c0 < Cin; c0 += 16) {
+            float av[8], bv[8], mv[8];
+            kb_ld8(xr + c0, av);
+            kb_ld8(mr + c0, mv);
+            kb_ld8(ar + c0, bv);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                av[j] = live ? av[j] - mv[j] : 0.f;
+                bv[j] = -bv[j];
+            }
+            acc = kb_step(av, bv, acc);
+        }
+        vc = v[cb * 32 + r];
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int mm = m0 + (i & 3) + 8 * (i >> 2) + 4 * h;
+        if (mm < M) dx[(int64_t)mm * ldd + cb * 32 + r] = acc[i] - vc;
+    }
+}
+
+// Cin = 3: thread = source row
+__global__ __launch_bounds__(KB_T) void kb_dx3_kernel(const float *__restrict__ gout, const float *__restrict__ outv, const unsigned char *__restrict__ win,
+                                                      const int *__restrict__ sel, int64_t ss, const float *__restrict__ w, const float *__restrict__ coef,
+                                                      const float *__restrict__ x, int64_t ldx, const float *__restrict__ mean, const float *__restrict__ am,
+                                                      const float *__restrict__ v, int dense, int M, int dim, int F, float *__restrict__ dx, int64_t ldd)
+{
+    const int m = blockIdx.x * KB_T + threadIdx.x;
+    if (m >= M) return;
+    const int b = m / dim, p = m - b * dim;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    for (int q = 0; q < 3; ++q) {
+        int n;
+        if (!kd_fed_row(b, p, q, dim, sel, ss, n)) continue;
+        const int64_t at = (((int64_t)b * dim + n) >> 1) * F;
+        const unsigned par = (unsigned)(n & 1);
+        for (int f = 0; f < F; ++f) {
+            const float d = (outv[at + f] > 0.f && win[at + f] == par) ? gout[at + f] * coef[3 * f + q] : 0.f;
+            const float *wr = w + (int64_t)(3 * f + q) * 3;
+            a0 = fmaf(d, wr[0], a0);
+            a1 = fmaf(d, wr[1], a1);
+            a2 = fmaf(d, wr[2], a2);
+        }
+    }
+    if (dense) {
+        const float *xr = x + (int64_t)m * ldx;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float t = xr[c] - mean[c];
+            a0 = fmaf(-t, am[3 * c], a0);
+            a1 = fmaf(-t, am[3 * c + 1], a1);
+            a2 = fmaf(-t, am[3 * c + 2], a2);
+        }
+        a0 -= v[0]; a1 -= v[1]; a2 -= v[2];
+    }
+    float *o = dx + (int64_t)m * ldd;
+    o[0] = a0; o[1] = a1; o[2] = a2;
+}
+
+// ---- host -------------------------------------------------------------------------------------------------------------------------------
+static bool kb_ok(int dim, int Cin, int F)
+{
+    return dim >= 2 && dim % 2 == 0 && (Cin == 3 || (Cin >= 32 && Cin <= 512 && Cin % 32 == 0)) && F >= 32 && F <= 1024 && F % 32 == 0;
+}
+
+static int kb_shape_ok(const char *who, int B, int dim, int Cin, int F)
+{
+    PAPC_REQUIRE(dim >= 2 && dim % 2 == 0, PAPC_E_UNSUPPORTED, "%s: dim=%d (points per cloud: even, >= 2)", who, dim);
+    PAPC_REQUIRE(Cin == 3 || (Cin >= 32 && Cin <= 512 && Cin % 32 == 0), PAPC_E_UNSUPPORTED, "%s: Cin=%d (3, or a multiple of 32 up to 512)", who, Cin);
+    PAPC_REQUIRE(F >= 32 && F <= 1024 && F % 32 == 0, PAPC_E_UNSUPPORTED, "%s: F=%d (a multiple of 32 up to 1024)", who, F);
+    PAPC_REQUIRE(B >= 1 && (int64_t)B * dim <= ((int64_t)1 << 28), PAPC_E_INVALID, "%s: B=%d dim=%d (B >= 1, B * dim <= 2^28)", who, B, dim);
+    return PAPC_OK;
+}
+
+static size_t kb_pad4(size_t n) { return (n + 3) & ~(size_t)3; }             // floats: every block of a workspace stays 16-byte aligned
+static int64_t kb_mchunks(int64_t M) { return cdiv(M, KB_MCH); }
+static int64_t kb_chunks(int64_t M, int Cin) { return cdiv(M, Cin == 3 ? KB_CH3 : KB_CH); }
+// kb_a_kernel's slices of the 3F channels: about 2048 waves in all, at least 8 k steps each; 1 = written in place, no fold
+static int kb_a_slices(int Cin, int F)
+{
+    if (Cin == 3) return 1;
+    const int ncb = Cin / 32, ks = 3 * F / 16;
+    return std::max(1, std::min(2048 / (ncb * ncb), ks / 8));
+}
+
+}  // namespace papc
+
+using namespace papc;
+
+extern "C" {
+
+int papc_kdbn_ok(int dim, int Cin, int F) { return kb_ok(dim, Cin, F) ? 1 : 0; }
+
+// workspace of the train-mode forward: [column-sum partials | second-moment partials | C]
+size_t papc_kdbn_fwd_workspace(int B, int dim, int Cin, int F)
+{
+    if (B < 1 || !kb_ok(dim, Cin, F) || (int64_t)B * dim > ((int64_t)1 << 28)) return 0;
+    const size_t T = (size_t)kb_mchunks((int64_t)B * dim), cc = (size_t)Cin * Cin;
+    return (kb_pad4(T * Cin) + kb_pad4(T * cc) + kb_pad4(cc)) * sizeof(float);
+}
+
+int papc_kdbn_fwd_f32(const float *x, int64_t ldx, const int32_t *sel, int64_t sel_stride, const float *w, const float *bias, const float *gamma,
+                      const float *beta, float *running_mean, float *running_var, int B, int dim, int Cin, int F, float eps, float momentum, int training,
+                      float *out, uint8_t *win, float *zhat, float *mean, float *tmat, float *stats, void *workspace, size_t workspace_bytes,
+                      papc_stream_t stream)
+{
+    const char *who = "papc_kdbn_fwd_f32";
+    PAPC_REQUIRE(x && sel && w && gamma && beta && out && win && zhat && stats, PAPC_E_INVALID, "%s: null pointer", who);
+    const int err = kb_shape_ok(who, B, dim, Cin, F);
+    if (err != PAPC_OK) return err;
+    PAPC_REQUIRE(ldx >= Cin && (sel_stride == 0 || sel_stride >= dim), PAPC_E_INVALID, "%s: ldx=%lld < Cin or sel_stride=%lld (0 or >= dim)", who,
+                 (long long)ldx, (long long)sel_stride);
+    PAPC_REQUIRE(Cin == 3 || (ldx % 4 == 0 && aligned16(x) && aligned16(w)), PAPC_E_INVALID, "%s: x and w must be 16-byte aligned, ldx=%lld a multiple of 4",
+                 who, (long long)ldx);
+    hipStream_t st = as_stream(stream);
+    const int M = B * dim, n_ch = 3 * F;
+    if (training) {
+        PAPC_REQUIRE(mean && tmat && workspace, PAPC_E_INVALID, "%s: train mode needs mean, tmat and a workspace", who);
+        const size_t need = papc_kdbn_fwd_workspace(B, dim, Cin, F);
+        PAPC_REQUIRE(workspace_bytes >= need && aligned16(workspace) && aligned16(mean) && aligned16(tmat), PAPC_E_INVALID,
+                     "%s: workspace %zu bytes < %zu (or workspace / mean / tmat not 16-byte aligned)", who, workspace_bytes, need);
+        const int T = (int)kb_mchunks(M);
+        const size_t cc = (size_t)Cin * Cin;
+        float *psum = static_cast<float *>(workspace), *pgram = psum + kb_pad4((size_t)T * Cin), *cm = pgram + kb_pad4((size_t)T * cc);
+        {
+            ProfScope prof(PAPC_K_MISC, st);
+            hipLaunchKernelGGL(kb_colsum_kernel, dim3((unsigned)T, (unsigned)cdiv(Cin, 16)), dim3(KB_T), 0, st, x, ldx, M, Cin, psum);
+            hipLaunchKernelGGL(kb_mean_kernel, dim3((unsigned)cdiv(Cin, KB_T)), dim3(KB_T), 0, st, psum, T, M, Cin, mean);
+            if (Cin == 3)
+                hipLaunchKernelGGL(kb_gram3_kernel, dim3((unsigned)T), dim3(KB_T), 0, st, x, ldx, mean, M, pgram);
+            else
+                hipLaunchKernelGGL(kb_gram_kernel, dim3((unsigned)T, (unsigned)cdiv((int64_t)(Cin / 32) * (Cin / 32), 4)), dim3(KB_T), 0, st, x, ldx, mean, M,
+                                   Cin, pgram);
+            const int e = check_launch("papc_kdbn_fwd_f32: moments");
+            if (e != PAPC_OK) return e;
+        }
+        int e = papc_reduce_partials_f32(pgram, T, (int64_t)cc, cm, 0, stream);          // the chunks in chunk order (fold.h)
+        if (e != PAPC_OK) return e;
+        ProfScope prof(PAPC_K_MISC, st);
+        if (Cin == 3)
+            hipLaunchKernelGGL(kb_t3_kernel, dim3((unsigned)cdiv(n_ch, KB_T)), dim3(KB_T), 0, st, w, cm, n_ch, tmat);
+        else
+            hipLaunchKernelGGL(kb_t_kernel, dim3((unsigned)(n_ch / 32), (unsigned)cdiv(Cin / 32, 4)), dim3(KB_T), 0, st, w, cm, Cin, tmat);
+        hipLaunchKernelGGL(kb_finalize_kernel, dim3((unsigned)n_ch), dim3(64), 0, st, w, bias, mean, tmat, M, Cin, n_ch, eps, momentum, stats, running_mean,
+                           running_var);
+        e = check_launch("papc_kdbn_fwd_f32: statistics");
+        if (e != PAPC_OK) return e;
+    } else {
+        PAPC_REQUIRE(running_mean && running_var, PAPC_E_INVALID, "%s: eval mode needs the running statistics", who);
+        ProfScope prof(PAPC_K_MISC, st);
+        hipLaunchKernelGGL(kb_eval_kernel, dim3((unsigned)cdiv(n_ch, KB_T)), dim3(KB_T), 0, st, bias, running_mean, running_var, n_ch, eps, stats);
+    }
+    ProfScope prof(PAPC_K_MLP_GEMM, st);
+    if (Cin == 3)
+        hipLaunchKernelGGL(kb_fwd3_kernel, dim3((unsigned)cdiv((int64_t)(M / 2) * F, KB_T)), dim3(KB_T), 0, st, x, ldx, sel, sel_stride, w, stats, gamma, beta, M,
+                           dim, F, out, win, zhat);
+    else
+        hipLaunchKernelGGL(kb_fwd_kernel, dim3((unsigned)cdiv(M, 32), (unsigned)cdiv(F / 32, 4)), dim3(KB_T), 0, st, x, ldx, sel, sel_stride, w, stats, gamma,
+                           beta, M, dim, Cin, F, out, win, zhat);
+    return check_launch(who);
+}
+
+// workspace of the backward: [chunk partials (S | dbeta | dgamma) | S | dbeta, dgamma | coefficients 3 x 3F | A | v | A, v per slice]
+size_t papc_kdbn_bwd_workspace(int B, int dim, int Cin, int F)
+{
+    if (B < 1 || !kb_ok(dim, Cin, F) || (int64_t)B * dim > ((int64_t)1 << 28)) return 0;
+    const size_t T = (size_t)kb_chunks((int64_t)B * dim, Cin), n1 = kb_pad4((size_t)3 * F * Cin), n2 = (size_t)6 * F;
+    const size_t na = kb_pad4((size_t)Cin * Cin) + kb_pad4(Cin), S = (size_t)kb_a_slices(Cin, F);
+    return (T * (n1 + n2) + n1 + n2 + (size_t)9 * F + na + (S > 1 ? S * na : 0)) * sizeof(float);
+}
+
+int papc_kdbn_bwd_f32(const float *gout, const float *out, const uint8_t *win, const float *zhat, const float *x, int64_t ldx, const int32_t *sel,
+                      int64_t sel_stride, const float *w, const float *gamma, const float *mean, const float *tmat, const float *stats, int B, int dim,
+                      int Cin, int F, int training, float *dx, int64_t ldd, float *dw, float *dbias, float *dgamma, float *dbeta, int accumulate,
+                      void *workspace, size_t workspace_bytes, papc_stream_t stream)
+{
+    const char *who = "papc_kdbn_bwd_f32";
+    PAPC_REQUIRE(gout && out && win && zhat && x && sel && w && gamma && stats && dw && dgamma && dbeta && workspace, PAPC_E_INVALID, "%s: null pointer", who);
+    const int err = kb_shape_ok(who, B, dim, Cin, F);
+    if (err != PAPC_OK) return err;
+    PAPC_REQUIRE(!training || (mean && tmat), PAPC_E_INVALID, "%s: train mode needs the forward's mean and tmat", who);
+    PAPC_REQUIRE(ldx >= Cin && (sel_stride == 0 || sel_stride >= dim) && (!dx || ldd >= Cin), PAPC_E_INVALID,
+                 "%s: ldx=%lld < Cin, ldd=%lld < Cin or sel_stride=%lld (0 or >= dim)", who, (long long)ldx, (long long)ldd, (long long)sel_stride);
+    PAPC_REQUIRE(Cin == 3 || (aligned16(gout) && aligned16(out) && (reinterpret_cast<uintptr_t>(win) & 7) == 0 && aligned16(x) && ldx % 4 == 0 &&
+                              (!training || aligned16(mean))),
+                 PAPC_E_INVALID, "%s: gout, out, x and mean must be 16-byte aligned, ldx a multiple of 4, the winner bytes 8-byte aligned", who);
+    const size_t need = papc_kdbn_bwd_workspace(B, dim, Cin, F);
+    PAPC_REQUIRE(workspace_bytes >= need && aligned16(workspace), PAPC_E_INVALID, "%s: workspace %zu bytes < %zu (or not 16-byte aligned)", who, workspace_bytes,
+                 need);
+    hipStream_t st = as_stream(stream);
+    const int M = B * dim, n_ch = 3 * F, T = (int)kb_chunks(M, Cin), dense = training ? 1 : 0;
+    const int64_t n1 = (int64_t)kb_pad4((size_t)n_ch * Cin), n2 = (int64_t)2 * n_ch;
+    float *part = static_cast<float *>(workspace), *S = part + (int64_t)T * (n1 + n2), *dbg = S + n1, *coef = dbg + n2, *am = coef + 3 * n_ch,
+          *v = am + kb_pad4((size_t)Cin * Cin);
+    {
+        ProfScope prof(PAPC_K_BWD_DW, st);
+        if (Cin == 3)
+            hipLaunchKernelGGL(kb_dw3_kernel, dim3((unsigned)T, (unsigned)(F / 32)), dim3(KB_T), 0, st, gout, out, win, zhat, x, ldx, sel, sel_stride, M, dim, F,
+                               part, n1 + n2);
+        else
+            hipLaunchKernelGGL(kb_dw_kernel, dim3((unsigned)T, (unsigned)cdiv((int64_t)(F / 32) * (Cin / 32), 4)), dim3(KB_T), 0, st, gout, out, win, zhat, x, ldx,
+                               sel, sel_stride, M, dim, Cin, F, part, n1 + n2);
+        const int e = check_launch("papc_kdbn_bwd_f32: S");
+        if (e != PAPC_OK) return e;
+    }
+    // the chunks in chunk order (fold.h)
+    int e = papc_reduce_partials2_f32(part, T, n1 + n2, n1, S, n2, dbg, 0, stream);
+    if (e != PAPC_OK) return e;
+    {
+        ProfScope prof(PAPC_K_BWD_DW, st);
+        hipLaunchKernelGGL(kb_dwfin_kernel, dim3((unsigned)cdiv((int64_t)n_ch * Cin, KB_T)), dim3(KB_T), 0, st, S, dbg, stats, gamma, mean, tmat, M, Cin, n_ch,
+                           training ? 0 : 1, accumulate, dw, dbias, dgamma, dbeta, coef);
+        e = check_launch("papc_kdbn_bwd_f32: dW");
+        if (e != PAPC_OK) return e;
+    }
+    if (!dx) return PAPC_OK;
+    if (dense) {
+        int S = 1, ks_per = n_ch / 16;
+        const int64_t na = (int64_t)Cin * Cin + Cin;                                           // (v follows A: a slice's layout)
+        float *apart = am;
+        {
+            ProfScope prof(PAPC_K_BWD_DX, st);
+            if (Cin == 3)
+                hipLaunchKernelGGL(kb_a3_kernel, dim3(1), dim3(64), 0, st, w, coef, n_ch, am, v);
+            else {
+                ks_per = (int)cdiv(n_ch / 16, kb_a_slices(Cin, F));
+                S = (int)cdiv(n_ch / 16, ks_per);
+                if (S > 1) apart = v + kb_pad4(Cin);
+                hipLaunchKernelGGL(kb_a_kernel, dim3((unsigned)cdiv((int64_t)(Cin / 32) * (Cin / 32), 4), (unsigned)S), dim3(KB_T), 0, st, w, coef, Cin, n_ch,
+                                   ks_per, apart);
+            }
+            e = check_launch("papc_kdbn_bwd_f32: A");
+            if (e != PAPC_OK) return e;
+        }
+        if (S > 1) {
+            e = papc_reduce_partials_f32(apart, S, na, am, 0, stream);                         // the slices in slice order (fold.h)
+            if (e != PAPC_OK) return e;
+        }
+    }
+    ProfScope prof(PAPC_K_BWD_DX, st);
+    if (Cin == 3)
+        hipLaunchKernelGGL(kb_dx3_kernel, dim3((unsigned)cdiv(M, KB_T)), dim3(KB_T), 0, st, gout, out, win, sel, sel_stride, w, coef, x, ldx, mean, am, v, dense, M,
+                           dim, F, dx, ldd);
+    else
+        hipLaunchKernelGGL(kb_dx_kernel, dim3((unsigned)cdiv(M, 32), (unsigned)cdiv(Cin / 32, 4)), dim3(KB_T), 0, st, gout, out, win, sel, sel_stride, w, coef, x,
+                           ldx, mean, am, v, dense, M, dim, Cin, F, dx, ldd);
+    return check_launch("papc_kdbn_bwd_f32: dX");
+}
+
+}  // extern "C"

@@ -22,35 +22,13 @@
 // Products: bf16x3.h on v_mfma_f32_32x32x16_bf16 (fp32 accuracy, fp32 accumulation).  The Cin = 3 first level runs fmaf chains on the vector
 // unit (kd_fwd3_kernel, kd_dx3_kernel, kd_dw3_kernel).  Plain C++ loads and stores only.
 #include "bf16x3.h"
+#include "kdsel.h"      // the select's index rule (kd_row_info, kd_fed_row), shared with kdbn.hip
 
 namespace papc {
 
 constexpr int KD_T = 256;        // threads of every kernel here (4 waves)
 constexpr int KD_CH = 128;       // rows per dW chunk (MFMA kernel)
 constexpr int KD_CH3 = 256;      // rows per dW chunk (Cin = 3 kernel)
-constexpr unsigned KD_ROW = 0x3fffffffu;
-
-__device__ __forceinline__ float4 kd_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ int kd_clamp_s(int s) { return min(max(s, 0), 2); }
-
-// pre-pool row m of the flattened rows -> (plane k << 30) | flattened source row; k = 3 for a row past M.  A split value outside 0..2 is
-// clamped, so it cannot address outside the buffers.
-__device__ __forceinline__ unsigned kd_row_info(int m, int M, int dim, const int *__restrict__ sel, int64_t ss)
-{
-    if (m >= M) return 3u << 30;
-    const int b = m / dim, n = m - b * dim;
-    const int j = 3 * n + kd_clamp_s(sel[(int64_t)b * ss + n]);
-    const int k = (j >= dim) + (j >= 2 * dim);
-    return ((unsigned)k << 30) | (unsigned)(b * dim + j - k * dim);
-}
-
-// the row of cloud b that source point p feeds through plane q, if any: 3n + s = p + q dim with s = sel[n]
-__device__ __forceinline__ bool kd_fed_row(int b, int p, int q, int dim, const int *__restrict__ sel, int64_t ss, int &n)
-{
-    const int t = p + q * dim;
-    n = t / 3;
-    return kd_clamp_s(sel[(int64_t)b * ss + n]) == t - 3 * n;
-}
 
 __device__ __forceinline__ void kd_store_pair(float y0, float y1, float *__restrict__ out, unsigned char *__restrict__ win, int64_t at)
 {

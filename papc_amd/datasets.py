@@ -182,6 +182,39 @@ def KDClasDataLoader(max_point=1024, batchsize=64, path='./data/', mode='train',
     return KDClasDataGenerator
 
 
+def KDSegDataLoader(max_point=1024, batchsize=64, path='./data/', mode='train', opener=None):
+    """kdloader.py:60-111.  As KDClasDataLoader, with the per-point part labels (the files' ``pid``) permuted by the tree's leaf order along with
+    the points (tools/build_KDTree.py:55-61).  Each call of the returned function = one epoch of
+    ``([points [b, 3, n] f32, split dims [b, 2n - 2] int32], label [b, n, 1] i64)``; models.KDUNet reads the first five levels of the split
+    dims.  The reference yields one cloud per step whatever ``batchsize`` says (kdloader.py:105-109); ``batchsize=1`` reproduces it."""
+    levels = int((np.log(max_point) / np.log(2)).astype(int))                                      # kdloader.py:61
+    opener = opener or default_opener
+    n = 1 << levels
+    points, splits, labels = [], [], []
+    for name in _files_of(mode):
+        f = opener(os.path.join(path, name))
+        data = np.asarray(f['data'])[:, :max_point, :]
+        pid = np.asarray(f['pid'])[:, :max_point]
+        for cloud, lab in zip(data, pid):
+            dims, order = kd_split_dims(cloud, levels)                                             # kdloader.py:89-91
+            splits.append(np.concatenate(dims).astype(np.int32))
+            points.append(np.ascontiguousarray(cloud[order].T, dtype=np.float32))                  # point_tree[-1].transpose(0, 2, 1), :92
+            labels.append(lab[order].astype(np.int64).reshape(n, 1))                               # label_tree[-1].transpose(1, 0), :93, :106
+    points = np.stack(points) if points else np.zeros((0, 3, n), np.float32)
+    splits = np.stack(splits) if splits else np.zeros((0, 2 * n - 2), np.int32)
+    labels = np.stack(labels) if labels else np.zeros((0, n, 1), np.int64)
+    index_list = list(range(len(points)))
+
+    def KDSegDataGenerator():
+        if mode == 'train':
+            random.shuffle(index_list)                                                             # kdloader.py:103-104
+        for lo in range(0, len(index_list), batchsize):
+            sel = index_list[lo:lo + batchsize]
+            yield [points[sel], splits[sel]], labels[sel]
+
+    return KDSegDataGenerator
+
+
 _PN_MODELS = ('pointnet_basic', 'pointnet', 'vfe', 'pointnet2_ssg', 'pointnet2_msg')
 
 

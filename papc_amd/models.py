@@ -7,6 +7,7 @@
   PointNet_Seg (T-Net PointNet)            <- /root/reference/PAPC/models/segment/pointnet/pointnet.py:4-114
   PointNet_Basic_Seg                       <- /root/reference/PAPC/models/segment/pointnet_base/pointnet_base.py:4-80
   KDNet                                    <- PAPC/models/classify/kdnet/kdnet.py:5-49
+  KDUNet                                   <- PAPC/models/segment/kdunet/kdunet.py:5-115
 
 Inputs are ``[B,3,N]`` float32 (``[B,6,N]`` with normals).  Everything runs in libpapc_hip.so, in train AND eval mode, the FC heads included
 (head.py); the nn.Linear / BatchNorm1d / Dropout modules are the parameter holders.  CPU tensors raise PapcError (there is no CPU path); the
@@ -582,3 +583,115 @@ class KDNet(nn.Module):
         for i, dim in enumerate(kdnet.DIMS):                                                     # :35-44
             rows = kdnet.kdconv(rows, kdnet.level_split_dims(sel, i), getattr(self, "conv%d" % (i + 1)), B, dim)
         return linear_rows(rows, self.fc.weight, self.fc.bias)                                   # :45-46 ([B, 128, 1] -> [B, 128])
+
+
+class _ConvBNReLU(nn.Module):
+    """ConvBNReLU of kdunet.py:20-39: the holder of a 1x1 conv and its norm under the source's names"""
+
+    def __init__(self, cin, cout):
+        super().__init__()
+        self._conv = nn.Conv1d(cin, cout, 1, 1)
+        self._batch_norm = nn.BatchNorm1d(cout, eps=1e-5)
+
+
+class _KDUNetDown(nn.Module):
+    LEVELS = ((1024, 3, 32), (512, 32, 64), (256, 64, 256), (128, 256, 512), (64, 512, 1024))      # (dim, Cin, F), kdunet.py:44-48, :65-69
+
+    def __init__(self):
+        super().__init__()
+        for i, (_, cin, f) in enumerate(self.LEVELS):
+            setattr(self, "convbnrelu%d" % (i + 1), _ConvBNReLU(cin, f * 3))
+
+
+class _KDUNetUp(nn.Module):
+    WIDTHS = ((1024, 512, 1024, 512), (512, 512, 768, 512), (512, 256, 320, 256), (256, 256, 288, 128), (128, 128, 131, 128))   # kdunet.py:77-96
+
+    def __init__(self, num_classes):
+        super().__init__()
+        for i, (cin, cup, ccat, cout) in enumerate(self.WIDTHS):
+            setattr(self, "deconv%d" % (i + 1), nn.ConvTranspose1d(cin, cup, 2, 2))
+            second = _ConvBNReLU(cout, cout) if i < 4 else nn.Conv1d(cout, num_classes, 1, 1)
+            setattr(self, "doubleconv%d" % (i + 1), nn.Sequential(_ConvBNReLU(ccat, cout), second))
+
+
+class KDUNet(nn.Module):
+    """KDUNet part segmenter (PAPC/models/segment/kdunet/kdunet.py:5-115).  Down: five levels of Conv1D(Cin, 3F, 1) + BatchNorm + ReLU + kd-tree
+    select + pair max (1024 points -> 32), each one kdnet.kdconv_bn node (csrc/kdbn.hip: only the selected third of the conv is computed, the
+    BatchNorm statistics of all 3F channels come from the moments of the level's input rows).  Up: five times Conv1DTranspose(k = 2, s = 2) as a
+    row GEMM (linear.linear_rows against the weight permuted to [2 Cout, Cin]: out[2i + t] = x[i] W[:, :, t] + bias), the concat with the level's
+    input rows (deconv first), and the ConvBNReLU pair on the shared-MLP stack without the max; the closing Conv1D(128, num_classes) on
+    linear_rows.  Module names and shapes are the source's, so checkpoint.export_state / import_state exchange .pdparams with it directly.
+
+    forward(inputs): inputs = [points, split_dims].  points [B, 3, 1024] (numpy or a device tensor); split_dims as for KDNet (only the first
+    five levels are read) or a list of just the first five arrays.  -> [B, 1024, num_classes]"""
+
+    def __init__(self, num_classes=50):
+        super().__init__()
+        self.downsample = _KDUNetDown()
+        self.upsample = _KDUNetUp(num_classes)
+
+    @staticmethod
+    def _pack5(split_dims, B, device):
+        """a list of just the first five levels -> the packed form (the five levels KDUNet never reads are zeros)"""
+        import numpy as np
+        from . import kdnet
+        items = split_dims if isinstance(split_dims, (list, tuple)) else [split_dims]
+        if any((isinstance(v, torch.Tensor) and v.is_floating_point()) or (isinstance(v, np.ndarray) and v.dtype.kind not in "iu") for v in items):
+            raise _lib.PapcError("KDUNet split dims: integer values (0, 1 or 2) expected, got a non-integer array")
+        if isinstance(split_dims, (list, tuple)) and len(split_dims) == 5:
+            per_cloud = any(getattr(v, "ndim", 1) == 2 for v in split_dims)
+            if all(isinstance(v, torch.Tensor) and v.is_cuda for v in split_dims):
+                rest = [torch.zeros((B, d) if per_cloud else (d,), dtype=torch.int32, device=device) for d in kdnet.DIMS[5:]]
+            else:
+                rest = [np.zeros((B, d) if per_cloud else (d,), np.int32) for d in kdnet.DIMS[5:]]
+            split_dims = list(split_dims) + rest
+        return kdnet.pack_split_dims(split_dims, B, device)
+
+    def _cbr(self, blocks, B, N, x_rows):
+        """relu(bn(conv(.))) x the ConvBNReLU blocks on the fused stack, every row kept: rows [B*N, C] -> [B*N, C_L]"""
+        convs, bns = [m._conv for m in blocks], [m._batch_norm for m in blocks]
+        spec = StackSpec(B, N, 1, N, 0, xyz_first=True, eps=bns[0].eps, momentum=0.9, pool=False, eval_bn=not self.training)
+        return shared_mlp_max(spec, _bn_buffers(bns), None, None, None, None, _stack_params(convs, bns), x_rows=x_rows)
+
+    def forward(self, inputs):
+        import numpy as np
+        from . import kdnet
+        from .copyops import contiguous_copy
+        from .linear import linear_rows
+        points, split_dims = inputs[0], inputs[1]
+        if isinstance(points, np.ndarray):                                                       # :12 paddle.to_tensor
+            dev = next(self.parameters()).device
+            if dev.type != "cuda":
+                raise _lib.PapcError("KDUNet needs its parameters on a CUDA (ROCm) device: there is no CPU fallback")
+            points = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).to(dev)
+        x = torch.as_tensor(points).float()
+        if not x.is_cuda or next(self.parameters()).device != x.device:
+            raise _lib.PapcError("KDUNet needs CUDA (ROCm) tensors and parameters on one device: there is no CPU fallback")
+        if x.dim() != 3 or x.shape[1] != 3:
+            raise _lib.PapcError("KDUNet: points [B, 3, %d] expected, got %s" % (kdnet.DIMS[0], tuple(x.shape)))
+        B, _, N = x.shape
+        if N != kdnet.DIMS[0]:
+            raise _lib.PapcError("KDUNet: the source's five levels halve %d points down to 32: N = %d points per cloud, %d expected"
+                                 % (kdnet.DIMS[0], N, kdnet.DIMS[0]))
+        sel = self._pack5(split_dims, B, x.device)
+        rows = contiguous_copy(x.transpose(1, 2)).view(B * N, 3)                                 # the planar coordinates as point rows
+        shortcut = []
+        for i, (dim, _, _) in enumerate(_KDUNetDown.LEVELS):                                     # :65-69
+            shortcut.append(rows)
+            blk = getattr(self.downsample, "convbnrelu%d" % (i + 1))
+            rows = kdnet.kdconv_bn(rows, kdnet.level_split_dims(sel, i), blk._conv, blk._batch_norm, B, dim, self.training)
+        up = self.upsample
+        n = kdnet.DIMS[5]                                                                        # 32 points per cloud
+        for i in range(5):                                                                       # :99-113
+            dc, pair = getattr(up, "deconv%d" % (i + 1)), getattr(up, "doubleconv%d" % (i + 1))
+            cin, cup = dc.weight.shape[0], dc.weight.shape[1]
+            w2 = contiguous_copy(dc.weight.permute(2, 1, 0)).view(2 * cup, cin)                  # [Cin, Cout, 2] -> rows t * Cout + co
+            rows = linear_rows(rows, w2, dc.bias.repeat(2) if dc.bias is not None else None).view(2 * B * n, cup)
+            n *= 2
+            rows = cat_copy([rows.unsqueeze(0), shortcut[4 - i].unsqueeze(0)], 2).squeeze(0)     # deconv first, then the level's input rows
+            if i < 4:
+                rows = self._cbr(list(pair), B, n, rows)
+            else:
+                rows = self._cbr([pair[0]], B, n, rows)
+                rows = linear_rows(rows, pair[1].weight, pair[1].bias)
+        return rows.view(B, N, -1)                                                               # :16 the final transpose: [B, N, classes]
