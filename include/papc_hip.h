@@ -756,6 +756,51 @@ int papc_kdbn_bwd_f32(const float *gout, const float *out, const uint8_t *win, c
                       int Cin, int F, int training, float *dx, int64_t ldd, float *dw, float *dbias, float *dgamma, float *dbeta, int accumulate,
                       void *workspace, size_t workspace_bytes, papc_stream_t stream);
 
+/* ---- VoxNet: implicit-GEMM 3-D convolutions (voxconv.hip) -------------------------------------- */
+/* The backbone of PAPC/models/classify/voxnet/voxnet.py:7-13 for an input edge E: Conv3D(1, 32, 5, stride 2) -> E1 = (E - 5) / 2 + 1, BatchNorm(32),
+ * LeakyReLU(0.01), Conv3D(32, 32, 3) -> E2 = E1 - 2, MaxPool3D(2, 2) -> Ep = E2 / 2.  x [B, E^3]; y1 [B E1^3, 32] is the pre-norm conv1 output,
+ * channel-last; w1 [32, 125], w2 [32, 32, 27], the source's shapes.  All products bf16x3 MFMA (fp32 accuracy), no atomics, fixed-order folds.
+ *   voxconv_ok           != 0 where the kernels take the edge: E <= 32, E1 >= 3, E2 even.  The calls below return PAPC_E_UNSUPPORTED elsewhere.
+ *   voxconv_parts        rows of the two partial buffers: ceil(B E1^3 / 128).
+ *   voxconv1_fwd         y1 = conv1(x) + b1 and stats_partial [parts, 2, 32] = per-workgroup (sum y, sum y^2): feed the BatchNorm finalize with
+ *                        n_tiles = parts, M = B E1^3.
+ *   voxconv2_prep        wk [32][27][32] = W2[co][tap][ci], wt [32][27][32] = W2[ci][tap][co]: the K-major orders the two calls below read.
+ *   voxconv2_pool_fwd    out [B, 32 Ep^3] (the source's flatten order c Ep^3 + p) = maxpool(conv2(leaky(scale y1 + shift)) + b2), win [B Ep^3, 32] the
+ *                        winner of each 2x2x2 group (0..7 = dz 4 + dy 2 + dx; the first on an exact tie).  The pre-pool tensor is never stored.
+ *   voxconv2_bwd_dx      gout [B, 32 Ep^3] -> gp [B Ep^3, 32] (its channel-last copy, kept for voxconv2_bwd_dw), dz [B E1^3, 32] = the gradient of
+ *                        the norm's output (LeakyReLU' from the sign of scale y1 + shift) and red_partial [parts, 2, 32] = (sum dz, sum dz xhat):
+ *                        feed the BatchNorm backward finalize.
+ *   voxconv2_bwd_dw      dw2 [32, 32, 27] and db2 [32] (NULL: skipped), written or (accumulate) added.
+ *   voxconv1_bwd_dw      dw1 [32, 125] from dy1 = scale (dz - c1 - xhat c2) formed on load; db1 (NULL: skipped) receives the exact zeros of a bias
+ *                        under a train-mode norm (nothing under accumulate).  The input receives no gradient.
+ * y1, scale, shift, wk, wt, gp and the workspaces 16-byte aligned, win 8-byte aligned. */
+int papc_voxconv_ok(int E);
+int papc_voxconv_parts(int B, int E);
+int papc_voxconv1_fwd_f32(const float *x, const float *w1, const float *b1, int B, int E, float *y1, float *stats_partial, papc_stream_t stream);
+int papc_voxconv2_prep_f32(const float *w2, float *wk, float *wt, papc_stream_t stream);
+int papc_voxconv2_pool_fwd_f32(const float *y1, const float *scale, const float *shift, const float *wk, const float *b2, int B, int E, float *out,
+                               uint8_t *win, papc_stream_t stream);
+int papc_voxconv2_bwd_dx_f32(const float *gout, const uint8_t *win, const float *wt, const float *y1, const float *mean, const float *invstd,
+                             const float *scale, const float *shift, int B, int E, float *gp, float *dz, float *red_partial, papc_stream_t stream);
+size_t papc_voxconv2_bwd_dw_workspace(int B, int E);
+int papc_voxconv2_bwd_dw_f32(const float *gp, const uint8_t *win, const float *y1, const float *scale, const float *shift, int B, int E, float *dw2,
+                             float *db2, int accumulate, void *workspace, size_t workspace_bytes, papc_stream_t stream);
+size_t papc_voxconv1_bwd_dw_workspace(int B, int E);
+int papc_voxconv1_bwd_dw_f32(const float *dz, const float *y1, const float *mean, const float *invstd, const float *scale, const float *c1, const float *c2,
+                             const float *x, int B, int E, float *dw1, float *db1, int accumulate, void *workspace, size_t workspace_bytes,
+                             papc_stream_t stream);
+/* out = dropout(leaky_relu(x, slope)) over n elements, upscale-in-train: the mask is the head's counter hash of rng_state = {seed, counter}
+ * (device int64[2]; NULL or drop_p == 0: no dropout), element index and `tag`; bump != 0: counter += 1 behind the draw.  keep [n] (uint8,
+ * nullable) receives the mask; the backward takes it back (NULL: everything kept). */
+int papc_leaky_dropout_fwd_f32(const float *x, int64_t n, float slope, float drop_p, int64_t *rng_state, int tag, int bump, float *out, uint8_t *keep,
+                               papc_stream_t stream);
+int papc_leaky_dropout_bwd_f32(const float *gout, const float *x, const uint8_t *keep, int64_t n, float slope, float drop_p, float *dx,
+                               papc_stream_t stream);
+/* grid [B, E^3] = 1.0 at (int(x h + h), int(y h + h), int(z h + h)), h = (E - 1) / 2, of every point of points [B, N, 3], else 0.0
+ * (PAPC/datasets/tools/build_VoxData.py:58-60); the index in double, product and sum rounded separately.  A coordinate outside [-1, 1] is
+ * clamped and counted in err [1]. */
+int papc_occupancy_grid_f32(const float *points, int B, int N, int E, float *grid, uint32_t *err, papc_stream_t stream);
+
 /* Axis-aligned bitmask NMS: nms_gpu of pointpillars/libs/ops/non_max_suppression/nms_gpu.py:130-164 (CUDA twin
  * libs/ops/cc/nms/nms_kernel.cu.cc:38-157), all on the device.  dets [N,5] = (x1, y1, x2, y2, score) fp32, N <= 65536.
  * keep [N] int32 receives the ORIGINAL indices of the kept boxes in descending-score order (ties: higher index first, the

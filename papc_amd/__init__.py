@@ -5,12 +5,14 @@ Public surface mirrors the reference:
   papc_amd.layers      <- PointNetSetAbstraction(.Msg)
   papc_amd.pillars     <- PFNLayer / PillarFeatureNet (pointpillars/models/bones/pillars.py)
   papc_amd.models      <- PointNet2_SSG_Clas / PointNet2_MSG_Clas / PointNet_Basic_Clas / PointNet_Clas (T-Net PointNet),
-                          PointNet2_SSG_Seg / PointNet2_MSG_Seg / PointNet_Seg / PointNet_Basic_Seg, KDNet, KDUNet
+                          PointNet2_SSG_Seg / PointNet2_MSG_Seg / PointNet_Seg / PointNet_Basic_Seg, KDNet, KDUNet, VoxNet
   papc_amd.transform   <- the T-Net PointNet's per-cloud transform x . T[b] and its T-Net FC blocks
   papc_amd.segment     <- the PointNet segmenters' first seg_net layer over concat([point, tile(global)]) without the tile
   papc_amd.kdnet       <- one KD-Net level (conv, ReLU, kd-tree select, pair max) computing only the selected third of the conv, and the KDUNet
                           down level (the same behind a BatchNorm whose statistics come from the input rows' moments)
-  papc_amd.datasets    <- PAPC/datasets loaders: PNClasDataLoader / PNSegDataLoader / KDClasDataLoader / KDSegDataLoader
+  papc_amd.voxnet      <- the VoxNet backbone (two 3-D convs as implicit GEMMs, the norm on load, the pool in registers), the head's LeakyReLU +
+                          dropout and the occupancy grid of a cloud
+  papc_amd.datasets    <- PAPC/datasets loaders: PNClasDataLoader / PNSegDataLoader / KDClasDataLoader / KDSegDataLoader / VoxDataLoader
 The compute lives in libpapc_hip.so (hand-written HIP, C ABI in include/papc_hip.h).
 """
 __version__ = "0.1.0"

@@ -163,6 +163,19 @@ SIGNATURES = {
     "papc_kdbn_bwd_workspace": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
     "papc_kdbn_bwd_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_l, c_p, c_p, c_p, c_p, c_i,
                                 c_p, ctypes.c_size_t, c_p]),
+    "papc_voxconv_ok": (c_i, [c_i]),
+    "papc_voxconv_parts": (c_i, [c_i, c_i]),
+    "papc_voxconv1_fwd_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p]),
+    "papc_voxconv2_prep_f32": (c_i, [c_p, c_p, c_p, c_p]),
+    "papc_voxconv2_pool_fwd_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p]),
+    "papc_voxconv2_bwd_dx_f32": (c_i, [c_p] * 8 + [c_i, c_i, c_p, c_p, c_p, c_p]),
+    "papc_voxconv2_bwd_dw_workspace": (ctypes.c_size_t, [c_i, c_i]),
+    "papc_voxconv2_bwd_dw_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_p, ctypes.c_size_t, c_p]),
+    "papc_voxconv1_bwd_dw_workspace": (ctypes.c_size_t, [c_i, c_i]),
+    "papc_voxconv1_bwd_dw_f32": (c_i, [c_p] * 8 + [c_i, c_i, c_p, c_p, c_i, c_p, ctypes.c_size_t, c_p]),
+    "papc_leaky_dropout_fwd_f32": (c_i, [c_p, c_l, c_f, c_f, c_p, c_i, c_i, c_p, c_p, c_p]),
+    "papc_leaky_dropout_bwd_f32": (c_i, [c_p, c_p, c_p, c_l, c_f, c_f, c_p, c_p]),
+    "papc_occupancy_grid_f32": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
     "papc_nms_workspace": (ctypes.c_size_t, [c_i]),
     "papc_nms_f32": (c_i, [c_p, c_i, c_f, c_p, c_p, c_p, ctypes.c_size_t, c_p]),
     "papc_lingather_parts": (c_i, [c_l]),

@@ -12,6 +12,7 @@
 // Dropout uses a counter-based hash of (seed, step counter, layer, element) read from device memory, so a captured hipGraph
 // draws fresh masks on every replay.
 #include "common.h"
+#include "hashrng.h"
 
 namespace papc {
 
@@ -22,15 +23,6 @@ constexpr int HW = 8;               // waves: K split
 constexpr int HROWS_MAX = 256;      // batch rows a workgroup can hold in LDS
 constexpr int TP = 33;              // LDS tile pitch (floats)
 constexpr int HC_STAGE_FLOATS = 16384;   // chain kernels: a [B, C] operand handed over by the previous phase is staged in LDS up to this size (64 KB)
-
-__device__ __forceinline__ float hash_uniform(uint64_t seed, uint64_t counter, uint32_t tag, uint32_t idx)
-{
-    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (counter + 1) + ((uint64_t)tag << 40) + idx;   // splitmix64 finaliser
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);   // 24 bits -> [0,1)
-}
 
 // ---- one launch for a chain of layers (head_chain_fwd_kernel / head_chain_bwd_kernel below) ---------------------------------------------
 // Inside a replayed graph a dependent launch costs >= 4.7 us before its first instruction (profiles/r05_*: a one-workgroup kernel with

@@ -215,16 +215,54 @@ def KDSegDataLoader(max_point=1024, batchsize=64, path='./data/', mode='train', 
     return KDSegDataGenerator
 
 
+# PAPC/datasets/tools/build_VoxData.py:4-39: the ten ModelNet categories of the voxel lists
+category = {'bathtub': 0, 'bed': 1, 'chair': 2, 'door': 3, 'dresser': 4, 'airplane': 5, 'piano': 6, 'sofa': 7, 'person': 8, 'cup': 9}
+categoryList = ['bathtub', 'bed', 'chair', 'door', 'dresser', 'airplane', 'piano', 'sofa', 'person', 'cup']
+
+
+def VoxDataLoader(max_point=1024, batchsize=64, path='./data/', mode='train'):
+    """voxloader.py:5-41.  ``path``/train.txt (``mode == 'train'``) or ``path``/test.txt lists one ``<grid .npy> <category>`` per line
+    (build_VoxData.py:64-78); every grid is loaded at construction.  A grid path is opened as written -- the source's lists are relative to the
+    working directory -- or, where that does not exist, relative to ``path``.  Each call of the returned function = one epoch of
+    ``(grids [b, 1, 32, 32, 32] f32, label [b, 1] i64)``; train mode shuffles the order in place with the global ``random`` module
+    (voxloader.py:25-26); the last batch may be short (:38-39).  ``max_point`` is unused, as in the source.  voxnet.occupancy_grid_np builds a
+    grid from a cloud (build_VoxData.py:58-60)."""
+    file_path = os.path.join(path, 'train.txt' if mode == 'train' else 'test.txt')               # :6-9
+    datas, labels = [], []
+    with open(file_path) as f:
+        for data_list in f:                                                                      # :14-17
+            name = data_list.split(' ')[0]
+            if not os.path.isabs(name) and not os.path.exists(name):
+                name = os.path.join(path, name)
+            datas.append(np.load(name))
+            labels.append(category[data_list.split(' ')[1].split('\n')[0]])
+    datas = np.array(datas)                                                                      # :19-20
+    labels = np.array(labels)
+    index_list = list(range(len(datas)))
+
+    def VoxDataGenerator():
+        if mode == 'train':
+            random.shuffle(index_list)                                                           # :25-26
+        for lo in range(0, len(index_list), batchsize):                                          # :29-39, a batch as one gather
+            sel = index_list[lo:lo + batchsize]
+            yield datas[sel].reshape(len(sel), 1, 32, 32, 32).astype('float32'), labels[sel].reshape(len(sel), 1).astype('int64')
+
+    return VoxDataGenerator
+
+
 _PN_MODELS = ('pointnet_basic', 'pointnet', 'vfe', 'pointnet2_ssg', 'pointnet2_msg')
 
 
 def DataLoader(model_name, max_point, batchsize, path='./data/', mode1='clas', mode2='train', opener=None):
-    """dataloader.py:5-40: the dispatcher train.py calls.  The point-set models (every model this library covers) share the PN loaders; the
-    KD-tree and voxel loaders belong to model families outside this library's scope and are reported as such."""
+    """dataloader.py:5-40: the dispatcher train.py calls.  The point-set models share the PN loaders and 'voxnet' gets the voxel loader
+    (dataloader.py:14-15); the KD-tree loaders (KDClasDataLoader, KDSegDataLoader) are called directly and reported here as outside the
+    point-set loaders."""
     if mode1 == 'clas':
         if model_name in _PN_MODELS:
             return PNClasDataLoader(max_point, batchsize, path, mode2, opener)
-        if model_name in ('voxnet', 'kdnet'):
+        if model_name == 'voxnet':
+            return VoxDataLoader(max_point, batchsize, path, mode2)
+        if model_name == 'kdnet':
             raise SystemExit('Error: the %s loader is outside this library (point-set models only)' % model_name)
         raise SystemExit('Error: model is incorrect')
     elif mode1 == 'seg':

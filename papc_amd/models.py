@@ -8,6 +8,7 @@
   PointNet_Basic_Seg                       <- /root/reference/PAPC/models/segment/pointnet_base/pointnet_base.py:4-80
   KDNet                                    <- PAPC/models/classify/kdnet/kdnet.py:5-49
   KDUNet                                   <- PAPC/models/segment/kdunet/kdunet.py:5-115
+  VoxNet                                   <- PAPC/models/classify/voxnet/voxnet.py:4-26
 
 Inputs are ``[B,3,N]`` float32 (``[B,6,N]`` with normals).  Everything runs in libpapc_hip.so, in train AND eval mode, the FC heads included
 (head.py); the nn.Linear / BatchNorm1d / Dropout modules are the parameter holders.  CPU tensors raise PapcError (there is no CPU path); the
@@ -695,3 +696,51 @@ class KDUNet(nn.Module):
                 rows = self._cbr([pair[0]], B, n, rows)
                 rows = linear_rows(rows, pair[1].weight, pair[1].bias)
         return rows.view(B, N, -1)                                                               # :16 the final transpose: [B, N, classes]
+
+
+class VoxNet(nn.Module):
+    """VoxNet classifier (PAPC/models/classify/voxnet/voxnet.py:4-26): Conv3D(1, 32, 5, 2) + BatchNorm + LeakyReLU + Conv3D(32, 32, 3) + MaxPool3D(2)
+    over a 32^3 occupancy grid, then Linear(6912, 128) + LeakyReLU + Dropout(0.2) + Linear(128, num_classes).  The backbone is one
+    voxnet.voxconv_backbone node (csrc/voxconv.hip: implicit-GEMM convs, the norm on load, the pool in registers), both Linear layers are
+    linear.linear_rows with voxnet.leaky_dropout between them.  The module tree is the source's (``backbone`` / ``head`` Sequentials), so the
+    parameter names are ``backbone.0.weight`` ... ``head.3.bias`` and checkpoint.export_state / import_state exchange .pdparams with it directly.
+    ``model.eval()``: the norm on its running statistics, no dropout, nothing updated.
+
+    forward(inputs): the grid [B, 1, 32, 32, 32] float32 as the source's loader yields it (numpy) or a device tensor -> [B, num_classes]"""
+
+    def __init__(self, name_scope='VoxNet_', num_classes=10):
+        super().__init__()
+        self.backbone = nn.Sequential(nn.Conv3d(1, 32, 5, 2), nn.BatchNorm3d(32), nn.LeakyReLU(), nn.Conv3d(32, 32, 3, 1), nn.MaxPool3d(2, 2, 0))     # :7-13
+        self.head = nn.Sequential(nn.Linear(32 * 6 * 6 * 6, 128), nn.LeakyReLU(), nn.Dropout(0.2), nn.Linear(128, num_classes))                       # :14-19
+
+    @property
+    def head_spec(self):
+        """the dropout's device rng state and mask export (head.HeadSpec), created on first use"""
+        spec = self.__dict__.get("_head_spec")
+        if spec is None:
+            spec = self.__dict__["_head_spec"] = _head.HeadSpec()
+        return spec
+
+    def forward(self, inputs):
+        import numpy as np
+        from . import voxnet
+        from .linear import linear_rows
+        dev = next(self.parameters()).device
+        if isinstance(inputs, np.ndarray):                                                       # :21 paddle.to_tensor
+            if dev.type != "cuda":
+                raise _lib.PapcError("VoxNet needs its parameters on a CUDA (ROCm) device: there is no CPU fallback")
+            if inputs.dtype != np.float32:
+                raise _lib.PapcError("VoxNet takes a float32 grid, got %s" % inputs.dtype)
+            inputs = torch.from_numpy(np.ascontiguousarray(inputs)).to(dev)
+        x = inputs
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or dev != x.device:
+            raise _lib.PapcError("VoxNet needs CUDA (ROCm) tensors and parameters on one device: there is no CPU fallback")
+        if x.dtype != torch.float32:
+            raise _lib.PapcError("VoxNet takes a float32 grid, got %s" % x.dtype)
+        if x.dim() != 5 or tuple(x.shape[1:]) != (1, voxnet.EDGE, voxnet.EDGE, voxnet.EDGE):
+            raise _lib.PapcError("VoxNet: a grid [B, 1, %d, %d, %d] expected, got %s" % (voxnet.EDGE, voxnet.EDGE, voxnet.EDGE, tuple(x.shape)))
+        b, h = self.backbone, self.head
+        x = voxnet.voxconv_backbone(x, b[0], b[1], b[3], self.training)                          # :22-23 (flattened: [B, 6912])
+        x = linear_rows(x, h[0].weight, h[0].bias)                                               # :15
+        x = voxnet.leaky_dropout(self.head_spec, x, h[2].p, self.training)                       # :16-17
+        return linear_rows(x, h[3].weight, h[3].bias)                                            # :18
