@@ -350,7 +350,9 @@ int papc_reduce_partials_f32(const float *partial, int n_chunks, int64_t n, floa
 /* two outputs from ONE partial buffer whose chunk rows are [n1 | n2] floats with row stride ld (the dW and db
  * partials of papc_mlp_bwd_dw_f32 laid out back to back): out1[i] (+)= sum_t partial[t*ld + i], out2[j] likewise */
 /* count <= 8 reductions of the papc_reduce_partials2_f32 kind in ONE launch (`jobs` is a HOST array read during the call): the dW / db
- * partials of every layer of a stack folded at the end of its backward instead of one launch-latency-sized kernel per layer */
+ * partials of every layer of a stack folded at the end of its backward instead of one launch-latency-sized kernel per layer.
+ * The jobs run concurrently and unordered: the CALLER passes outputs (out1 / out2 ranges) that are pairwise distinct, as the layers of
+ * one stack are -- jobs that share an output go into separate calls (or through papc_fold_jobs_f32, which orders them itself). */
 typedef struct papc_reduce_job {
     const float *partial;   /* [n_chunks][ld] */
     int32_t n_chunks;
@@ -367,7 +369,12 @@ int papc_reduce_partials2_f32(const float *partial, int n_chunks, int64_t ld, in
  *     out[r * out_ld + c] (+)= sum_{t < n_chunks} partial[t * ld + r * cols + c]      r < rows, c < cols      (fixed order: csrc/fold.h)
  * A training step folds the partials of ALL its stacks once, behind the last backward kernel, instead of 5-6 launch-latency-sized
  * kernels spread over the backward: papc_sa_mlp_bwd appends its jobs to papc_sa_grads.defer (a HOST list owned by the caller, who keeps
- * the backward scratch buffers alive until papc_fold_jobs_f32 has been enqueued) instead of launching them.  `jobs` is a HOST array. */
+ * the backward scratch buffers alive until papc_fold_jobs_f32 has been enqueued) instead of launching them.  `jobs` is a HOST array.
+ * ANY job list is safe, `count` is unbounded: jobs apply as if one after the other in list order.  The jobs of one launch run
+ * concurrently, so the call starts a new launch at a job whose output range [out, out + (rows-1)*out_ld + cols) overlaps that of a job
+ * already in the current launch (two accumulate jobs on one .grad: a module applied twice in one backward pass); two column blocks of
+ * one row-major matrix (equal out_ld, rows > 1, disjoint column intervals) count as disjoint.  A list without overlaps folds in
+ * ceil(count / PAPC_FOLD_MAX) launches. */
 #define PAPC_FOLD_MAX 24
 typedef struct papc_fold_job {
     const float *partial;   /* [n_chunks][ld] */

@@ -152,6 +152,19 @@ __global__ __launch_bounds__(64 * FW) void fold_jobs_kernel(FoldBatch b)
 
 using namespace papc;
 
+// Two fold jobs whose output RANGES intersect can still write disjoint elements: column blocks of one row-major matrix (the same row stride:
+// the xyz and the feature columns of the gather-add first layer's dW).  True only where that is certain.
+static bool disjoint_column_blocks(const papc_fold_job &a, const papc_fold_job &b)
+{
+    if (a.rows < 2 || b.rows < 2 || a.out_ld != b.out_ld) return false;
+    const bool a_first = (uintptr_t)a.out <= (uintptr_t)b.out;
+    const papc_fold_job &p = a_first ? a : b, &q = a_first ? b : a;
+    const uintptr_t bytes = (uintptr_t)q.out - (uintptr_t)p.out;
+    if (bytes % sizeof(float)) return false;
+    const int64_t c0 = (int64_t)(bytes / sizeof(float)) % p.out_ld;        // q's first column in p's row grid
+    return c0 >= p.cols && c0 + q.cols <= p.out_ld;                        // (q's rows do not wrap; p holds columns [0, p.cols))
+}
+
 extern "C" {
 
 int papc_reduce_partials2_f32(const float *partial, int n_chunks, int64_t ld, int64_t n1, float *out1, int64_t n2,
@@ -198,16 +211,28 @@ int papc_fold_jobs_f32(const papc_fold_job *jobs, int count, papc_stream_t strea
     PAPC_REQUIRE(count >= 1, PAPC_E_INVALID, "papc_fold_jobs_f32: count=%d", count);
     hipStream_t st = as_stream(stream);
     const int FW = knob(KNOB_FOLD_WAVES) == 16 ? 16 : 8;
-    for (int j0 = 0; j0 < count; j0 += PAPC_FOLD_MAX) {
-        const int nj = std::min(PAPC_FOLD_MAX, count - j0);
+    // The jobs of ONE launch run concurrently (a flat grid), and a job ends in a read-modify-write of its output: a launch holds only jobs
+    // whose output ranges [out, out + (rows - 1) * out_ld + cols) are pairwise disjoint.  A job that overlaps one of the current launch
+    // starts the next launch, so overlapping jobs apply in list order (a module applied twice in one backward pass queues two accumulate
+    // jobs on the same .grad); a list without overlaps -- every step without sharing -- still folds in ceil(count / PAPC_FOLD_MAX) launches.
+    for (int j0 = 0; j0 < count;) {
         FoldBatch b;
         memset(&b, 0, sizeof(b));
         int64_t wgs = 0;
-        for (int i = 0; i < nj; ++i) {
+        uintptr_t lo[PAPC_FOLD_MAX], hi[PAPC_FOLD_MAX];
+        int nj = 0;
+        for (; nj < PAPC_FOLD_MAX && j0 + nj < count; ++nj) {
+            const int i = nj;
             const papc_fold_job &j = jobs[j0 + i];
             PAPC_REQUIRE(j.partial && j.out, PAPC_E_INVALID, "papc_fold_jobs_f32: null pointer in job %d", j0 + i);
             PAPC_REQUIRE(j.n_chunks >= 1 && j.rows >= 1 && j.cols >= 1 && j.ld >= (int64_t)j.rows * j.cols && j.out_ld >= j.cols, PAPC_E_INVALID,
                          "papc_fold_jobs_f32: bad sizes in job %d", j0 + i);
+            lo[i] = (uintptr_t)j.out;
+            hi[i] = lo[i] + sizeof(float) * (uintptr_t)((int64_t)(j.rows - 1) * j.out_ld + j.cols);
+            bool overlaps = false;
+            for (int k = 0; k < i && !overlaps; ++k)
+                overlaps = lo[i] < hi[k] && lo[k] < hi[i] && !disjoint_column_blocks(jobs[j0 + k], j);
+            if (overlaps) break;                // (i >= 1 here: the launch below is never empty)
             const int64_t n = (int64_t)j.rows * j.cols;
             const bool wide = j.n_chunks <= 16 && n >= 16384 && n % 4 == 0 && j.ld % 4 == 0 && (j.rows == 1 || j.out_ld == j.cols) && aligned16(j.partial) && aligned16(j.out);
             b.part[i] = j.partial; b.out[i] = j.out; b.ld[i] = j.ld; b.out_ld[i] = j.out_ld; b.n_chunks[i] = j.n_chunks; b.rows[i] = j.rows; b.cols[i] = j.cols;
@@ -226,6 +251,7 @@ int papc_fold_jobs_f32(const papc_fold_job *jobs, int count, papc_stream_t strea
         else hipLaunchKernelGGL(fold_jobs_kernel<16>, dim3((unsigned)wgs), dim3(1024), 0, st, b);
         const int rc = check_launch("papc_fold_jobs_f32");
         if (rc != PAPC_OK) return rc;
+        j0 += nj;
     }
     return PAPC_OK;
 }

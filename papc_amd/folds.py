@@ -7,6 +7,8 @@ graph task id, so that a pass that raised and never ran its callbacks leaves not
 pass registers that list's ``flush`` as a final callback of the autograd engine, which runs it once every node of the pass
 has been enqueued -- still inside a hipGraph capture, and once per stage of a two-stage backward (bench.py, N > 1).  The backward scratch
 buffers the jobs read are kept alive until the fold has been enqueued.  ``PAPC_DEFER_FOLDS=0`` restores the per-stack launches.
+A module applied twice inside one pass (two augmentations through one model, shared weights) queues two accumulate jobs on the same ``.grad``:
+papc_fold_jobs_f32 applies overlapping jobs in list order, in launches of their own (tests/test_gpu_inplace.py, pattern (d)).
 
 Reference: the reference has no counterpart (Paddle's autograd accumulates dense gradients); this only changes WHEN this library's
 split reductions are folded, not what they add up to (same summation order per job: tests/test_gpu_cabi.py).

@@ -1,6 +1,7 @@
 """Deferred folds (papc_amd/folds.py, papc_fold_jobs_f32): the partial reductions of a whole backward pass in one launch.
 
-(i) the kernel against numpy on both of its shapes (many chunks / few chunks), strided outputs, accumulation;
+(i) the kernel against numpy on both of its shapes (many chunks / few chunks), strided outputs, accumulation -- and with jobs that share an
+output, which must apply in list order;
 (ii) a training step of PointNet2_SSG_Clas (reference: PAPC/models/classify/pointnet2/pointnet2.py:6-41, loop PAPC/train.py:106-116)
 with the folds deferred against the same step with every stack folding its own partials: identical losses, gradients equal up to
 the summation order of the strided / split-K jobs (the dW / db jobs keep their order and are bit-identical);
@@ -46,6 +47,88 @@ def test_fold_jobs_kernel_vs_numpy(dev):
         got = to.cpu().numpy()
         assert_close(got[:, :cols], ref[:, :cols], 2e-6, "fold job %d" % i)
         assert np.array_equal(got[:, cols:], ref[:, cols:].astype(np.float32)), "job %d wrote outside its block" % i
+
+
+FOLD_MAX = 24      # include/papc_hip.h: PAPC_FOLD_MAX, the jobs of one launch
+
+# Jobs that share ONE output buffer of 20 000 floats: (n_chunks, rows, cols, out_ld, first element, accumulate).  Every shape of the kernel
+# (csrc/folds.hip: papc_fold_jobs_f32 picks wide for n_chunks <= 16 and n >= 16384, the float4 lane fold for other contiguous n >= 1024,
+# else the lane fold), the same pointer twice in each of them, two strided column blocks that overlap in 12 of their 24 columns, and one
+# overwriting job between the two wide ones, so that any other order than the list's gives other values.
+_SHARING = [(4, 1, 16384, 16384, 0, 1),         # wide
+            (40, 1, 2048, 2048, 1024, 1),       # float4 lane fold
+            (37, 32, 24, 100, 515, 1),          # lane fold, a strided column block ...
+            (37, 32, 24, 100, 527, 1),          # ... and the block 12 columns to its right
+            (40, 1, 2048, 2048, 1024, 1),       # the float4 job's pointer again
+            (37, 1, 77, 77, 5, 1),              # lane fold
+            (3, 1, 300, 300, 6000, 0),          # overwrites what the jobs before it left there
+            (37, 1, 77, 77, 5, 1),              # the lane job's pointer again
+            (4, 1, 16384, 16384, 0, 1)]         # the wide job's pointer again
+_PRIVATE = [(64, 1, 192, 192, 0), (37, 16, 3, 19, 1), (8, 1, 1024, 1024, 0), (100, 1, 77, 77, 1)]      # (n_chunks, rows, cols, out_ld, accumulate)
+_NSHARED = 20000
+
+
+def _overlapping_jobs(total):
+    """``total`` jobs in list order: the sharing ones spread evenly, jobs on private outputs between them -> [(spec, private?)]"""
+    at = sorted({int(v) for v in np.round(np.linspace(0, total - 1, len(_SHARING)))})
+    assert len(at) == len(_SHARING)
+    order, k, f = [], 0, 0
+    for i in range(total):
+        if i in at:
+            order.append((_SHARING[k], False))
+            k += 1
+        else:
+            order.append((_PRIVATE[f % len(_PRIVATE)], True))
+            f += 1
+    return order
+
+
+def _run_overlapping(dev, order, seed):
+    lib = _lib.load()
+    rng = np.random.default_rng(seed)
+    shared0 = rng.normal(size=_NSHARED).astype(np.float32)
+    shared = torch.from_numpy(shared0).to(dev)
+    ref_shared = shared0.astype(np.float64)
+    jobs = (folds.FoldJob * len(order))()
+    keep, outs = [shared], [(shared, ref_shared)]
+    for i, (spec, private) in enumerate(order):
+        nc, rows, cols, out_ld = spec[:4]
+        off, acc = (0, spec[4]) if private else (spec[4], spec[5])
+        part = rng.normal(size=(nc, rows * cols)).astype(np.float32)
+        tp = torch.from_numpy(part).to(dev)
+        keep.append(tp)
+        if private:
+            out0 = rng.normal(size=rows * out_ld).astype(np.float32)
+            to, ref = torch.from_numpy(out0).to(dev), out0.astype(np.float64)
+            outs.append((to, ref))
+        else:
+            to, ref = shared, ref_shared
+        idx = off + np.arange(rows)[:, None] * out_ld + np.arange(cols)[None, :]
+        assert idx.max() < ref.size
+        blk = part.astype(np.float64).sum(0).reshape(rows, cols)
+        ref[idx] = (ref[idx] if acc else 0.0) + blk                      # float64, applied in list order
+        jobs[i] = folds.FoldJob(tp.data_ptr(), nc, acc, rows * cols, rows, cols, to.data_ptr() + 4 * off, out_ld)
+    _lib.check(lib.papc_fold_jobs_f32(jobs, len(order), _lib.stream_ptr()), "papc_fold_jobs_f32")
+    torch.cuda.synchronize()
+    return [(to.cpu().numpy(), ref) for to, ref in outs], shared0
+
+
+@pytest.mark.parametrize("total", [11, 40])
+def test_fold_jobs_with_overlapping_outputs_apply_in_list_order(dev, total):
+    """Accumulate jobs that share an output (a module applied twice inside one backward pass queues two jobs on one .grad): the result is the
+    float64 sum applied in LIST order at the bar of test_fold_jobs_kernel_vs_numpy (2e-6: each job is the same fold, and a job adds one fp32
+    rounding of the running value), with fewer and with more jobs than one launch takes (PAPC_FOLD_MAX = 24), and two calls on the same inputs
+    are bit-identical.  (The jobs of one launch run concurrently: before papc_fold_jobs_f32 split its launches at overlapping outputs, two
+    such jobs raced on the read-modify-write and one contribution was lost.)"""
+    assert (total < FOLD_MAX) == (total == 11)
+    order = _overlapping_jobs(total)
+    res1, shared0 = _run_overlapping(dev, order, 17)
+    res2, _ = _run_overlapping(dev, order, 17)
+    for i, ((got, ref), (again, _)) in enumerate(zip(res1, res2)):
+        assert np.array_equal(got, again), "output %d differs between two calls on the same inputs" % i
+        assert_close(got, ref, 2e-6, "overlapping fold jobs, output %d of %d jobs" % (i, total))
+    got = res1[0][0]
+    assert np.array_equal(got[16384:], shared0[16384:]), "a job wrote behind the shared blocks"
 
 
 def _step(dev, defer, graph):
