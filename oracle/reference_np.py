@@ -3,15 +3,15 @@
 Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline`` leg may import
 this package.  ``papc_amd`` never does; it fails loudly if its HIP library is missing.
 
-PARITY UNPINNED.  The reference (AgentMaker/PAPC) is pure Python on PaddlePaddle; it holds no
-tests, fixtures or golden vectors for this path, and PaddlePaddle cannot be installed in the build
-container, so this restatement could not be checked against an execution of the reference.  It
-follows the reference source line by line (``file:line`` citations are into
-``/root/reference/PAPC/models/layers/pointnet2_basic_layers.py`` unless another file is named),
-numpy standing in for paddle, with fp32 rounding order fixed to the canonical arithmetic of
-SURVEY.md section 8a (see ``papc_oracle.c``).  Second opinions available here: the same functions
-written literally (``*_literal`` below: tile/mask/sort exactly as the source does) and a torch-CPU
-transliteration (``torch_cpu_reference.py``); the tests check all three agree.
+PINNED BY EXECUTION, OP SEMANTICS ASSUMED.  The reference (AgentMaker/PAPC) is pure Python on PaddlePaddle and holds no tests, fixtures
+or golden vectors for this path.  Its own model code is executed on ``oracle/paddle_standin`` (a torch-CPU stand-in for the paddle names it
+uses) by ``tests/golden/make_reference_golden.py``; ``tests/test_reference_pin.py`` holds this restatement to what came out (indices exact,
+the float32-mode values bit for bit where nothing is accumulated).  What each Paddle op does stays an assumption, listed in the stand-in's
+docstring.  The restatement follows the reference source line by line (``file:line`` citations are into
+``PAPC/models/layers/pointnet2_basic_layers.py`` unless another file is named), numpy standing in for paddle, with fp32 rounding order
+fixed to the canonical arithmetic of SURVEY.md section 8a (see ``papc_oracle.c``).  Second opinions available here: the same functions
+written literally (``*_literal`` below: tile/mask/sort exactly as the source does) and a torch-CPU transliteration
+(``torch_cpu_reference.py``); the tests check all three agree.
 
 Layout conventions are the reference's: xyz ``[B,N,3]``, features ``[B,N,D]`` inside the free
 functions; layers take ``[B,C,N]``.

@@ -7,7 +7,9 @@ host round-trips per iteration (pointnet2_basic_layers.py:79-93), the dense [B,S
 tile + full sort of query_ball_point (:110-124), numpy fancy-index gathers that cut autograd (:57-60), and
 unfused Conv2d(1x1) / BatchNorm2d / relu / max (:215-219) -- with torch-CPU (MKL) standing in for paddle-CPU.
 It doubles as a second opinion for the oracle: tests check its indices equal the C restatement bit for bit.
-PARITY UNPINNED (no reference tests or fixtures exist; see reference_np.py).
+Run in double it is held at 1e-9 to the reference's own model code executed on the paddle stand-in (tests/test_reference_pin.py; see
+reference_np.py).  Its norms are torch's: they put the UNBIASED batch variance into running_var where Paddle puts the biased one, which
+nothing here reads (the pin tests redo that update the Paddle way).
 """
 import numpy as np
 import torch

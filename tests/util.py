@@ -66,6 +66,31 @@ def seeded_model_state(model, seed):
     return out
 
 
+def reference_weight(name, shape, seed):
+    """The rule (name, shape, seed) -> float32 array behind the tests/golden/ref_*.npz fixtures, which store no weights: the generator gives the
+    reference's models these values and the pin tests give them to this project's.  ``name`` / ``shape`` are the REFERENCE's (Linear weights
+    [in, out]); layers the reference holds in plain lists are named as this project names them (``sa1.mlp_convs.0.weight``).  Each array has
+    its own generator keyed by (seed, CRC-32 of the name), so the values do not depend on the order the names are visited in.
+    Matrices / kernels ~ N(0, 2 / fan_in); one-dimensional ``weight`` (only norms have one) in +-[0.5, 1.5] with a quarter negative;
+    one-dimensional ``bias`` ~ 0.1 N(0, 1) (0.2 N(0, 1) under a norm would need the layer type: one rule for both)."""
+    import zlib
+    rng = np.random.default_rng([int(seed), zlib.crc32(name.encode())])
+    shape = tuple(int(s) for s in shape)
+    if len(shape) >= 2:
+        fan_in = shape[0] if len(shape) == 2 else int(np.prod(shape[1:]))
+        a = rng.normal(size=shape) * np.sqrt(2.0 / fan_in)
+    elif name.endswith("weight"):
+        a = rng.uniform(0.5, 1.5, size=shape) * rng.choice([1.0, 1.0, 1.0, -1.0], size=shape)
+    else:
+        a = rng.normal(size=shape) * 0.1
+    return a.astype(np.float32)
+
+
+def reference_state(names, shapes, seed):
+    """{name: reference_weight(...)} for recorded (names, shapes) -- a reference-style state for papc_amd.checkpoint.import_state"""
+    return {str(n): reference_weight(str(n), tuple(s[s >= 0]) if isinstance(s, np.ndarray) else s, seed) for n, s in zip(names, shapes)}
+
+
 def copy_into_model(model, state):
     import torch
     with torch.no_grad():
