@@ -876,6 +876,21 @@ int papc_compact_corr_parts(void);
 int papc_bn_stats_corr_f32(const float *y, int C, const int32_t *start, const float *coef, int G, float *stats_rows, papc_stream_t stream);
 int papc_bn_relu_max_seg_f32(const float *y, int C, const int32_t *start, const float *scale, const float *shift, int G, float *out,
                              int32_t *argmax, float *ysel, papc_stream_t stream);
+/* The same neighbourhood max WITHOUT the pass over y: the forward of the max layer keeps the extremum of every ragged group itself.
+ * papc_mlp_gemm_rows_keys_f32: papc_mlp_gemm_rows_w_f32 for PAPC_A_BNRELU rows (y and stats_partial bit-identical to it) that also combines,
+ * by a 64-bit integer atomic max, keys [G, Cout] = {order-preserving image of max y (min y where sign_src[c] < 0, the layer's BatchNorm
+ * weight) : 0xFFFFFFFF - first row attaining it} over the groups seg_grp [rows / 8] names.  keys must hold ZEROS when the call starts
+ * (every written key is non-zero); an integer maximum is exact in any order, so the result is reproducible bit for bit.
+ * papc_mlp_seg_epi_ok says for which shapes it is built (Cin = 128, Cout % 128 == 0: the compacted 128 -> 256 layer); others are refused.
+ * papc_bn_relu_select_seg_f32: keys + the stored y -> out, argmax, ysel, bit for bit what papc_bn_relu_max_seg_f32 writes on that y
+ * (ties -> first row, +0 == -0, a NaN never wins, an all-NaN group -> its first row and -inf; a channel whose scale and sign_src
+ * disagree in sign -- NaN statistics -- is scanned as there). */
+int papc_mlp_seg_epi_ok(int64_t M, int Cin, int Cout);
+int papc_mlp_gemm_rows_keys_f32(const float *x, int64_t ldx, const float *bn_scale, const float *bn_shift, const float *w, const float *bias,
+                                int64_t M, int Cin, int Cout, float *y, float *stats_partial, const int32_t *rows_dev, const float *wrow,
+                                const int32_t *seg_grp, const float *sign_src, unsigned long long *keys, papc_stream_t stream);
+int papc_bn_relu_select_seg_f32(const unsigned long long *keys, const float *y, int C, const int32_t *start, const float *sign_src,
+                                const float *scale, const float *shift, int G, float *out, int32_t *argmax, float *ysel, papc_stream_t stream);
 int papc_lingather_fwd_f32(const float *P, const papc_group_src *grp, int B, const float *w, int ldw, int xcol0, const float *bias, int C,
                            float *y, float *stats_partial, papc_stream_t stream);
 int papc_lingather_bwd_f32(const papc_bwd_dy *dy, const papc_group_src *grp, int B, int C, float *G, float *dwx_partial, papc_stream_t stream);

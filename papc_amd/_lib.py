@@ -106,6 +106,9 @@ SIGNATURES = {
     "papc_mlp_compact_ok": (c_i, [c_l, c_i, c_i, c_p]),
     "papc_bn_stats_corr_f32": (c_i, [c_p, c_i, c_p, c_p, c_i, c_p, c_p]),
     "papc_bn_relu_max_seg_f32": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p]),
+    "papc_mlp_seg_epi_ok": (c_i, [c_l, c_i, c_i]),
+    "papc_mlp_gemm_rows_keys_f32": (c_i, [c_p, c_l, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "papc_bn_relu_select_seg_f32": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p]),
     "papc_bn_select_max_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_p, c_p, c_p]),
     "papc_bn_finalize_f32": (c_i, [c_p, c_i, c_l, c_i, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "papc_bn_relu_max_f32": (c_i, [c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p]),

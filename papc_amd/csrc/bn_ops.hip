@@ -70,15 +70,15 @@ __device__ __forceinline__ void fold_part_lanes(double &s1, double &s2)
 // ---------------------------------------------------------------------------------------------------
 // stats partials [n_tiles][2][C] -> mean, invstd, scale = gamma*invstd, shift = beta - mean*scale
 // ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void bn_finalize_kernel(const float *__restrict__ part, int n_tiles, int64_t M, int C,
-                                                        const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                        float eps, float momentum, float *mean, float *invstd, float *scale,
-                                                        float *shift, float *rmean, float *rvar)
+__device__ __forceinline__ void bn_finalize_channel(const int c, const float *__restrict__ part, int n_tiles, int64_t M, int C,
+                                                    const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                    float eps, float momentum, float *mean, float *invstd, float *scale,
+                                                    float *shift, float *rmean, float *rvar)
 {
     // ONE WAVE per channel, no LDS, <= 64 registers: a launch-sized kernel has to find room on a CU that another stream's persistent
     // GEMM has filled to the last KB of LDS (config 3 runs its MSG branches on three streams: the 1024-thread / 16 KB form of this
     // kernel waited 13-21 us on average, up to 0.3 ms, for a whole CU to drain).  Lane = part-lane.
-    const int c = blockIdx.x, tl = threadIdx.x;
+    const int tl = threadIdx.x;
     // (the channel's affine parameters and running statistics are requested ahead of the partial rows: one round trip, not two)
     const float gam = gamma ? gamma[c] : 1.f, bet = beta ? beta[c] : 0.f;
     const float rm0 = rmean ? rmean[c] : 0.f, rv0 = rvar ? rvar[c] : 0.f;
@@ -98,6 +98,33 @@ __global__ __launch_bounds__(64) void bn_finalize_kernel(const float *__restrict
         if (rmean) rmean[c] = momentum * rm0 + (1.f - momentum) * (float)mu;   // paddle: momentum weighs the running value
         if (rvar) rvar[c] = momentum * rv0 + (1.f - momentum) * (float)var;
     }
+}
+__global__ __launch_bounds__(64) void bn_finalize_kernel(const float *__restrict__ part, int n_tiles, int64_t M, int C,
+                                                        const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                        float eps, float momentum, float *mean, float *invstd, float *scale,
+                                                        float *shift, float *rmean, float *rvar)
+{
+    bn_finalize_channel(blockIdx.x, part, n_tiles, M, C, gamma, beta, eps, momentum, mean, invstd, scale, shift, rmean, rvar);
+}
+// The same launch with a buffer to clear riding on it (bn_finalize_clear, below): workgroups [0, C) are bn_finalize_kernel's, the ones
+// behind them each zero BN_CLEAR_PER_WG 16-byte pieces of clr[0, n16).  The launch is far below its floor (C one-wave workgroups), so the
+// extra workgroups run beside the channels' on idle CUs instead of as a launch of their own on the chain.
+constexpr int BN_CLEAR_PER_LANE = 16, BN_CLEAR_PER_WG = 64 * BN_CLEAR_PER_LANE;
+__global__ __launch_bounds__(64) void bn_finalize_clear_kernel(const float *__restrict__ part, int n_tiles, int64_t M, int C,
+                                                              const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                              float eps, float momentum, float *mean, float *invstd, float *scale,
+                                                              float *shift, float *rmean, float *rvar, uint4 *__restrict__ clr, int64_t n16)
+{
+    if ((int)blockIdx.x >= C) {
+        const int64_t i0 = (int64_t)((int)blockIdx.x - C) * BN_CLEAR_PER_WG + threadIdx.x;
+#pragma unroll
+        for (int q = 0; q < BN_CLEAR_PER_LANE; ++q) {
+            const int64_t i = i0 + q * 64;
+            if (i < n16) clr[i] = make_uint4(0u, 0u, 0u, 0u);
+        }
+        return;
+    }
+    bn_finalize_channel(blockIdx.x, part, n_tiles, M, C, gamma, beta, eps, momentum, mean, invstd, scale, shift, rmean, rvar);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -608,6 +635,22 @@ __global__ __launch_bounds__(256) void transpose_batch_kernel(TransposeBatch t)
         }
         __syncthreads();
     }
+}
+
+// papc_bn_finalize_f32 with `bytes` (a multiple of 16) of `clr` zeroed by the same launch (internal: sa_mlp.hip, the key buffer of the
+// ragged-group extremum epilogue).  Whatever is launched next on the stream finds the buffer cleared: kernel boundaries on one stream.
+int bn_finalize_clear(const float *stats_partial, int n_tiles, int64_t M, int C, const float *gamma, const float *beta, float eps, float momentum,
+                      float *mean, float *invstd, float *scale, float *shift, float *running_mean, float *running_var, void *clr, int64_t bytes,
+                      hipStream_t st)
+{
+    PAPC_REQUIRE(stats_partial && mean && invstd && scale && shift && clr, PAPC_E_INVALID, "bn_finalize_clear: null pointer");
+    PAPC_REQUIRE(n_tiles >= 1 && M >= 1 && C >= 1 && bytes >= 16 && bytes % 16 == 0 && aligned16(clr), PAPC_E_INVALID, "bn_finalize_clear: bad sizes");
+    const int64_t n16 = bytes / 16, nclr = cdiv(n16, BN_CLEAR_PER_WG);
+    PAPC_REQUIRE(nclr + C < (1ll << 31), PAPC_E_UNSUPPORTED, "bn_finalize_clear: %lld bytes", (long long)bytes);
+    ProfScope prof(PAPC_K_MISC, st);
+    hipLaunchKernelGGL(bn_finalize_clear_kernel, dim3((unsigned)(C + nclr)), dim3(64), 0, st, stats_partial, n_tiles, M, C, gamma, beta, eps, momentum,
+                       mean, invstd, scale, shift, running_mean, running_var, reinterpret_cast<uint4 *>(clr), n16);
+    return check_launch("bn_finalize_clear");
 }
 
 }  // namespace papc

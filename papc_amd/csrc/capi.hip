@@ -72,6 +72,7 @@ static const KnobDef g_knob_defs[KNOB_COUNT] = {
     {"PAPC_LG_PP", 1, 0, 1},               // gather-add backward over point lists WITHOUT re-reading y: dz stored masked by the dX above, y's share from P and the lists' moments (0: gathers y and dz)
     {"PAPC_PG_GROUP", 1, 0, 1},            // papc_pg_gemm_group_f32: a layer's dX and dW products in one grid (0: one launch per product)
     {"PAPC_PG_PIPE", 1, 0, 1},             // pg_gemm_kernel / pg_gemm_group_kernel: 1 = four-slot k16 LDS ring, DMA in flight across the barriers (0, and with PAPC_PG_DBG or PAPC_PG_NS=3: the k32 stage loop); measured in DESIGN 3.8
+    {"PAPC_SEG_EPI", 1, 0, 1},             // papc_sa_mlp_fwd, compacted pooled stack: the last layer's forward keeps the ragged groups' extrema (atomic-max keys) and a select kernel replaces seg_max_kernel's pass over y (0: that pass); bit-identical either way
 };
 static int g_knobs[KNOB_COUNT];
 static int knob_parse(int id, const char *e)

@@ -16,7 +16,8 @@
 //     over its copies, dy = s (p - w (c1 + xhat c2)) with w = wrow[row] = 1 + coef[g] on a group's first row and 1 elsewhere (p, the
 //     max / ReLU gradient, reaches a copy set once: the first-maximum rule picks its first row); the BN-backward sums over the rows of
 //     the summed gradient are the padded tensor's sums.
-//   * the neighbourhood max runs over a group's physical rows (seg_max_kernel), argmax = absolute row.
+//   * the neighbourhood max runs over a group's physical rows, argmax = absolute row: seg_max_kernel, a pass over the stored output -- or,
+//     where the last layer's forward has the ragged-group extremum epilogue, seg_select_kernel on the keys that epilogue left.
 //
 // Everything here is integer / streaming work on [G] and [rows, C] arrays: HBM- and latency-bound, no matrix cores.
 #include "common.h"
@@ -201,6 +202,67 @@ __global__ __launch_bounds__(256) void seg_max_kernel(const float *__restrict__ 
     *reinterpret_cast<float4 *>(ysel + q) = make_float4(ys[0], ys[1], ys[2], ys[3]);
 }
 
+// ---- forward: the same three arrays from the keys the layer's forward left (mlp_stream.hip, SG epilogue) -----------------------------------
+// keys[g, c] = {order-preserving image of the extreme compared value : 0xFFFFFFFF - its first row}, combined by the forward over the tiles of
+// group g.  Thread = (group, channel quad): decode the row and the value (ysel carries the stored bits; a zero's sign is read from y), apply
+// the BatchNorm + ReLU.  Bit for bit what seg_max_kernel writes, without its pass over y:
+//   * a high word at or below the image of -inf (0x007FFFFF) means nothing passed a strict comparison against -inf -- the group holds only
+//     NaN and / or the key -inf: seg_max_kernel's answer is the group's first row and -inf (with the channel's sign flip);
+//   * the forward chose max or min by the sign of the BatchNorm WEIGHT (its own statistics do not exist yet), seg_max_kernel chooses by
+//     scale = weight * invstd.  The two agree unless the statistics are NaN (an overflowed channel: scale >= 0 is false whatever the weight)
+//     or the product underflows to -0; such a channel is scanned here the way seg_max_kernel scans it -- a diverged stack's path, not the step's.
+__global__ __launch_bounds__(256) void seg_select_kernel(const unsigned long long *__restrict__ keys, const float *__restrict__ y, int C,
+                                                         const int32_t *__restrict__ start, const float *__restrict__ sign_src,
+                                                         const float *__restrict__ scale, const float *__restrict__ shift, int G,
+                                                         float *__restrict__ out, int32_t *__restrict__ argmax, float *__restrict__ ysel)
+{
+    const int CQ = C >> 2;
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)G * CQ) return;
+    const int g = (int)(e / CQ), c = (int)(e - (int64_t)g * CQ) * 4;
+    const int r0 = start[g], r1 = start[g + 1];
+    const int64_t q = (int64_t)g * C + c;
+    const float4 sc = *reinterpret_cast<const float4 *>(scale + c), sh = *reinterpret_cast<const float4 *>(shift + c);
+    const float4 gm = *reinterpret_cast<const float4 *>(sign_src + c);
+    const ulonglong2 k01 = *reinterpret_cast<const ulonglong2 *>(keys + q), k23 = *reinterpret_cast<const ulonglong2 *>(keys + q + 2);
+    const float s4[4] = {sc.x, sc.y, sc.z, sc.w}, h4[4] = {sh.x, sh.y, sh.z, sh.w}, g4[4] = {gm.x, gm.y, gm.z, gm.w};
+    const unsigned long long k4[4] = {k01.x, k01.y, k23.x, k23.y};
+    int flip[4], am[4];
+    bool scan[4];
+    float ys[4], o[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        flip[i] = s4[i] >= 0.f ? 0 : (int)0x80000000u;                                  // seg_max_kernel's rule
+        scan[i] = flip[i] != (g4[i] < 0.f ? (int)0x80000000u : 0);                      // ... against the forward's
+        const int row = (int)~(unsigned)k4[i];
+        const unsigned u = (unsigned)(k4[i] >> 32);
+        const bool hit = !scan[i] && u > 0x007FFFFFu && row >= r0 && row < r1;          // (a row outside the group is never read)
+        am[i] = hit ? row : r0;
+        // the image is a bijection but for -0, which it holds as +0: the compared value comes back out of the key, and with it the raw y
+        // (a gather of one float per (group, channel) would touch more than half of y's cache lines again); only a ZERO is looked up in y for its sign
+        const int kb = (u & 0x80000000u) ? (int)(u ^ 0x80000000u) : (int)~u;
+        ys[i] = hit ? __int_as_float(kb ^ flip[i]) : __int_as_float((int)0xFF800000u ^ flip[i]);
+        if (hit && kb == 0) ys[i] = y[(int64_t)row * C + c + i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (scan[i]) {
+            float mx = -INFINITY;
+            int ix = r0;
+            for (int r = r0; r < r1; ++r) {
+                const float k = __int_as_float(__float_as_int(y[(int64_t)r * C + c + i]) ^ flip[i]);
+                if (k > mx) { mx = k; ix = r; }
+            }
+            ys[i] = __int_as_float(__float_as_int(mx) ^ flip[i]);
+            am[i] = ix;
+        }
+        o[i] = relu_np(fmaf(s4[i], ys[i], h4[i]));
+    }
+    *reinterpret_cast<float4 *>(out + q) = make_float4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<int4 *>(argmax + q) = make_int4(am[0], am[1], am[2], am[3]);
+    *reinterpret_cast<float4 *>(ysel + q) = make_float4(ys[0], ys[1], ys[2], ys[3]);
+}
+
 }  // namespace papc
 
 using namespace papc;
@@ -245,6 +307,20 @@ int papc_bn_relu_max_seg_f32(const float *y, int C, const int32_t *start, const 
     ProfScope prof(PAPC_K_BN_RELU_MAX, st);
     hipLaunchKernelGGL(seg_max_kernel, dim3((unsigned)cdiv((int64_t)G * (C / 4), 256)), dim3(256), 0, st, y, C, start, scale, shift, G, out, argmax, ysel);
     return check_launch("papc_bn_relu_max_seg_f32");
+}
+
+int papc_bn_relu_select_seg_f32(const unsigned long long *keys, const float *y, int C, const int32_t *start, const float *sign_src, const float *scale,
+                                const float *shift, int G, float *out, int32_t *argmax, float *ysel, papc_stream_t stream)
+{
+    PAPC_REQUIRE(keys && y && start && sign_src && scale && shift && out && argmax && ysel, PAPC_E_INVALID, "papc_bn_relu_select_seg_f32: null pointer");
+    PAPC_REQUIRE(G >= 1 && C >= 4 && C % 4 == 0, PAPC_E_UNSUPPORTED, "papc_bn_relu_select_seg_f32: C=%d must be a multiple of 4", C);
+    PAPC_REQUIRE(aligned16(keys) && aligned16(sign_src) && aligned16(scale) && aligned16(shift) && aligned16(out) && aligned16(argmax) && aligned16(ysel),
+                 PAPC_E_INVALID, "papc_bn_relu_select_seg_f32: 16-byte alignment");
+    hipStream_t st = as_stream(stream);
+    ProfScope prof(PAPC_K_BN_RELU_MAX, st);
+    hipLaunchKernelGGL(seg_select_kernel, dim3((unsigned)cdiv((int64_t)G * (C / 4), 256)), dim3(256), 0, st, keys, y, C, start, sign_src, scale, shift, G,
+                       out, argmax, ysel);
+    return check_launch("papc_bn_relu_select_seg_f32");
 }
 
 }  // extern "C"

@@ -30,6 +30,10 @@ struct ScatterDst {
 struct GmaxDst {
     float *gmax, *gmin; int32_t *amax, *amin; int K;
     const float *sgn;      // papc_group_max::sign_src (row-streaming kernel: one extremum per channel instead of two)
+    // ragged groups of a compacted stack (SG flavour of the row-streaming forward): one packed {ordered value : 0xFFFFFFFF - row} key per
+    // (group, channel), combined across tiles, waves and workgroups by a 64-bit integer atomic max; seg = group of every 8-row segment
+    unsigned long long *keys;
+    const int32_t *seg;
 };
 
 struct GemmArgs {

@@ -1014,10 +1014,12 @@ int papc_mlp_gemm_f32(int a_mode, const float *x, int64_t ldx, const papc_group_
     return papc_mlp_gemm_rows_f32(a_mode, x, ldx, grp, bn_scale, bn_shift, w, bias, M, Cin, Cout, y, stats_partial, gmax, nullptr, stream);
 }
 
-int papc_mlp_gemm_rows_w_f32(int a_mode, const float *x, int64_t ldx, const papc_group_src *grp,
-                           const float *bn_scale, const float *bn_shift, const float *w, const float *bias,
-                           int64_t M, int Cin, int Cout, float *y, float *stats_partial, const papc_group_max *gmax,
-                           const int32_t *rows_dev, const float *wrow, papc_stream_t stream)
+// (one body for the row-GEMM forward entry points; seg_grp / sign_src / keys: papc_mlp_gemm_rows_keys_f32)
+static int gemm_rows_impl(int a_mode, const float *x, int64_t ldx, const papc_group_src *grp,
+                          const float *bn_scale, const float *bn_shift, const float *w, const float *bias,
+                          int64_t M, int Cin, int Cout, float *y, float *stats_partial, const papc_group_max *gmax,
+                          const int32_t *rows_dev, const float *wrow, const int32_t *seg_grp, const float *sign_src,
+                          unsigned long long *keys, papc_stream_t stream)
 {
     PAPC_REQUIRE(w && (y || gmax), PAPC_E_INVALID, "papc_mlp_gemm_f32: null w/y");
     PAPC_REQUIRE(!rows_dev || (!gmax && (a_mode == A_PLAIN || a_mode == A_BNRELU)), PAPC_E_UNSUPPORTED,
@@ -1031,6 +1033,8 @@ int papc_mlp_gemm_rows_w_f32(int a_mode, const float *x, int64_t ldx, const papc
     p.w = w; p.ldw = Cin; p.bias = bias; p.M = M; p.Kin = Cin; p.Nout = Cout; p.y = y; p.ldy = Cout; p.stats = stats_partial;
     p.rows_dev = rows_dev;
     p.wstat = rows_dev ? wrow : nullptr;
+    p.gm.keys = keys; p.gm.seg = seg_grp;
+    if (keys) p.gm.sgn = sign_src;
     p.wmap = (a_mode == A_GROUP) ? 1 : 0;  // GROUP: internal order [feats, xyz] -> caller's columns through gk()
     const bool vec = p.a.vec && (p.wmap || (aligned16(w) && Cin % 4 == 0));
     hipStream_t st = as_stream(stream);
@@ -1067,6 +1071,34 @@ int papc_mlp_gemm_rows_w_f32(int a_mode, const float *x, int64_t ldx, const papc
     case A_BNRELU: return launch_gemm<A_BNRELU, EPI_STORE>(p, vec, st);
     default: return launch_gemm<A_GROUP, EPI_STORE>(p, vec, st);
     }
+}
+
+int papc_mlp_gemm_rows_w_f32(int a_mode, const float *x, int64_t ldx, const papc_group_src *grp,
+                           const float *bn_scale, const float *bn_shift, const float *w, const float *bias,
+                           int64_t M, int Cin, int Cout, float *y, float *stats_partial, const papc_group_max *gmax,
+                           const int32_t *rows_dev, const float *wrow, papc_stream_t stream)
+{
+    return gemm_rows_impl(a_mode, x, ldx, grp, bn_scale, bn_shift, w, bias, M, Cin, Cout, y, stats_partial, gmax, rows_dev, wrow, nullptr, nullptr, nullptr, stream);
+}
+
+/* 1 when the storing BN+ReLU forward has its ragged-group extremum epilogue for these widths (papc_mlp_gemm_rows_keys_f32): 128 input
+ * channels, whole column blocks of 128 -- the compacted max layer 128 -> 256 -- on the row-streaming kernel's asm ring. */
+int papc_mlp_seg_epi_ok(int64_t M, int Cin, int Cout)
+{
+    if (!knob(KNOB_STREAM) || knob(KNOB_GEMM_F32) || !knob(KNOB_STREAM_ASM)) return 0;
+    if (M % 128 != 0 || M / 32 < knob(KNOB_STREAM_MINTILES)) return 0;
+    return Cin == 128 && Cout >= 128 && Cout % 128 == 0;
+}
+
+int papc_mlp_gemm_rows_keys_f32(const float *x, int64_t ldx, const float *bn_scale, const float *bn_shift, const float *w, const float *bias,
+                                int64_t M, int Cin, int Cout, float *y, float *stats_partial, const int32_t *rows_dev, const float *wrow,
+                                const int32_t *seg_grp, const float *sign_src, unsigned long long *keys, papc_stream_t stream)
+{
+    PAPC_REQUIRE(y && rows_dev && seg_grp && sign_src && keys, PAPC_E_INVALID, "papc_mlp_gemm_rows_keys_f32: null pointer");
+    PAPC_REQUIRE(((uintptr_t)keys & 7) == 0 && ((uintptr_t)seg_grp & 3) == 0, PAPC_E_INVALID, "papc_mlp_gemm_rows_keys_f32: keys must be 8-byte aligned");
+    PAPC_REQUIRE(papc_mlp_seg_epi_ok(M, Cin, Cout), PAPC_E_UNSUPPORTED, "papc_mlp_gemm_rows_keys_f32: not built for M=%lld Cin=%d Cout=%d (papc_mlp_seg_epi_ok)",
+                 (long long)M, Cin, Cout);
+    return gemm_rows_impl(PAPC_A_BNRELU, x, ldx, nullptr, bn_scale, bn_shift, w, bias, M, Cin, Cout, y, stats_partial, nullptr, rows_dev, wrow, seg_grp, sign_src, keys, stream);
 }
 
 int papc_mlp_gemm_rows_f32(int a_mode, const float *x, int64_t ldx, const papc_group_src *grp,

@@ -105,11 +105,22 @@ __device__ __forceinline__ floatx2_t pk_fma(floatx2_t a, floatx2_t b, floatx2_t 
 // GS (group-max epilogues): ONE extremum per channel -- the max of a channel whose BatchNorm weight is >= 0, the min of the others (GmaxDst::sgn,
 // papc_group_max::sign_src) -- followed as the maximum of the value with its sign bit flipped where the minimum is wanted; written to both pairs
 // of arrays, so papc_bn_select_max_f32 reads the same value whichever it picks.  Half the compare / select instructions of the epilogue.
+// SG (storing BN+ReLU forward of a compacted stack, device-side row count): the GS extremum over RAGGED groups.  A group is a multiple of 8
+// rows, starts anywhere and spans tiles of different waves and workgroups; in the accumulator layout r >> 2 is the 8-row segment, and a
+// segment lies inside one group (GmaxDst::seg, wave-uniform per segment).  One running (key, row) pair per column tile, closed when the
+// group changes between segments and at the end of the tile: the half-waves merge as in GS, then lanes 0-31 issue ONE returnless 64-bit
+// unsigned atomic max per close into GmaxDst::keys[g * Nout + col] -- high word an order-preserving integer image of the compared value
+// (-0 canonicalised to +0: the float comparisons it stands for hold them equal), low word 0xFFFFFFFF - row, so the first row wins ties.
+// A maximum under that rule is exact and independent of order: the bits are the same whichever workgroup arrives first, and they are the
+// bits seg_max_kernel (compact.hip) finds on the stored output.  A pair nothing has won yet (only NaN or the key -inf so far: neither
+// passes a strict comparison against the initial -inf) is sent as the image of -inf, which every real candidate beats and the select
+// kernel reads as "the group's first row, -inf", seg_max_kernel's answer.  Every key is non-zero: the buffer is cleared to 0.
 template <int AMODE, int EPI, int KB16, int CK, int WN, bool ASM, bool CP = false, int KV = KB16 * 16, bool NR = false, int CBW = WN * 32, bool PS = false, int NWT = 8,
-          bool GS = false>
+          bool GS = false, bool SG = false>
 __global__ __launch_bounds__(NWT * 64, NWT / 4) void stream_kernel(GemmArgs p, StreamGeo geo)
 {
     static_assert(!GS || EPI == EPI_STORE_GMAX || EPI == EPI_GMAX, "GS: group-max epilogues only");
+    static_assert(!SG || (EPI == EPI_STORE && AMODE == A_BNRELU && ASM && !CP && !NR && KV == KB16 * 16 && NWT == 8), "SG: the storing BN+ReLU forward of a compacted stack only");
     static_assert(NWT == 8 || NWT == 12, "two or three waves per SIMD");
     static_assert(!PS || (CP && AMODE == A_DY_MAX), "PS: the compacted max-layer dX only (the one flavour where the result is bit-identical)");
     static_assert(!CP || ((AMODE == A_DY_DENSE || AMODE == A_DY_MAX) && EPI == EPI_STORE_RED && ASM && PAPC_STREAM_PK), "CP: dX flavours of the asm ring only");
@@ -538,7 +549,7 @@ __global__ __launch_bounds__(NWT * 64, NWT / 4) void stream_kernel(GemmArgs p, S
         rsc[wn] = rsh[wn] = rmu[wn] = ris[wn] = 0.f;
         if (EPI == EPI_STORE_RED) { rsc[wn] = p.rd.scale[col]; rsh[wn] = p.rd.shift[col]; rmu[wn] = p.rd.mean[col]; ris[wn] = p.rd.invstd[col]; }
         gmx[wn] = -INFINITY; gmn[wn] = INFINITY; gix[wn] = 0; gin[wn] = 0;
-        if constexpr (GS) gin[wn] = (p.gm.sgn[col] < 0.f) ? (int)0x80000000u : 0;      // (GS: gin holds the channel's sign flip, gmn is unused)
+        if constexpr (GS || SG) gin[wn] = (p.gm.sgn[col] < 0.f) ? (int)0x80000000u : 0;      // (GS, SG: gin holds the channel's sign flip, gmn is unused)
     }
 
     // epilogue of the tile starting at row0 (sub = its index inside the unit).  C/D layout: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 hi.
@@ -569,6 +580,16 @@ __global__ __launch_bounds__(NWT * 64, NWT / 4) void stream_kernel(GemmArgs p, S
             }
             return;
         }
+        // SG: the groups of the tile's four 8-row segments.  A SCALAR load in inline asm, waited for in the same statement: the operand ring's
+        // chunk 1 of the next tile is in flight here, and a compiler-visible vector load beside hidden ones is what LATE1 (below) exists to avoid
+        [[maybe_unused]] int sgv[4] = {0, 0, 0, 0};
+        if constexpr (SG) {
+            typedef int i32x4 __attribute__((ext_vector_type(4)));
+            i32x4 q;
+            const int32_t *sp = p.gm.seg + (row0 >> 3);
+            asm volatile("s_load_dwordx4 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(q) : "s"(sp));
+            sgv[0] = q[0]; sgv[1] = q[1]; sgv[2] = q[2]; sgv[3] = q[3];
+        }
 #pragma unroll
         for (int wn = 0; wn < WN; ++wn) {
             const int col = n0 + wn * 32 + l31;
@@ -596,6 +617,8 @@ __global__ __launch_bounds__(NWT * 64, NWT / 4) void stream_kernel(GemmArgs p, S
                 }
                 }
             } else {
+                [[maybe_unused]] float bk = -INFINITY;      // SG: the open (key, row offset in the tile) pair of this lane's column
+                [[maybe_unused]] int bo = 0;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int ro = (r & 3) + 8 * (r >> 2);
@@ -603,6 +626,26 @@ __global__ __launch_bounds__(NWT * 64, NWT / 4) void stream_kernel(GemmArgs p, S
                     if (EPI != EPI_GMAX && cok) yp[(int64_t)ro * ldy] = v;   // (EPI_GMAX: under the max the output itself stays unwritten)
                     s1[wn] += v;
                     s2[wn] = fmaf(v, v, s2[wn]);
+                    if constexpr (SG) {
+                        const float key = __int_as_float(__float_as_int(v) ^ gin[wn]);      // (as GS: strict, the first row wins; a NaN never does)
+                        if (key > bk) { bk = key; bo = ro; }
+                        if ((r & 3) == 3 && ((r >> 2) == 3 || sgv[((r >> 2) + 1) & 3] != sgv[r >> 2])) {
+                            // close (wave-uniform branch): the group ends with this segment, or the tile does -- a wave's next tile is no neighbour
+                            float vmx = bk;
+                            int imx = row0 + 4 * hi + bo;
+                            const float omx = __shfl_xor(vmx, 32);
+                            const int oix = __shfl_xor(imx, 32);
+                            if (omx > vmx || (omx == vmx && oix < imx)) { vmx = omx; imx = oix; }
+                            if (hi == 0) {
+                                unsigned u = __float_as_uint(vmx);
+                                u = (u == 0x80000000u) ? 0u : u;                              // -0 and +0 compare equal
+                                u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);               // float order -> unsigned order
+                                const unsigned long long k = ((unsigned long long)u << 32) | (unsigned)~imx;
+                                __hip_atomic_fetch_max(p.gm.keys + (int64_t)sgv[r >> 2] * p.Nout + col, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            }
+                            bk = -INFINITY; bo = ro;
+                        }
+                    }
                     if (GM) {
                         const int off = sub * 32 + ro + 4 * hi;
                         if constexpr (GS) {
@@ -818,9 +861,10 @@ static int stream_ncu()
     return ncu;
 }
 
-template <int AMODE, int EPI, int KB16, int WN, bool CP = false, int KV = KB16 * 16, bool NR = false, int CBW = WN * 32, bool PS = false>
+template <int AMODE, int EPI, int KB16, int WN, bool CP = false, int KV = KB16 * 16, bool NR = false, int CBW = WN * 32, bool PS = false, bool SG = false>
 static int stream_go(const GemmArgs &p, const StreamGeo &geo, hipStream_t st)
 {
+    static_assert(!SG || (!CP && !PS), "SG: a forward flavour");
     // k blocks per prefetch chunk: two, unless the flavour's registers do not allow it (an asm-loaded buffer must never spill)
     constexpr bool KR = (KV != KB16 * 16);
     constexpr int KBF = KR ? KB16 - 1 : KB16;
@@ -848,6 +892,12 @@ static int stream_go(const GemmArgs &p, const StreamGeo &geo, hipStream_t st)
             hipLaunchKernelGGL((stream_kernel<AMODE, EPI, KB16, CK, WN, true, true>), grid, dim3(512), 0, st, p, geo);
         }
         const int rc = check_launch("mlp stream gemm (compacted)");
+        return rc ? rc : 1;
+    }
+    if constexpr (SG) {      // (asm ring only, like every device-row-count flavour)
+        if (!knob(KNOB_STREAM_ASM)) return 0;
+        hipLaunchKernelGGL((stream_kernel<AMODE, EPI, KB16, CK, WN, true, false, KV, NR, CBW, false, 8, false, true>), grid, dim3(512), 0, st, p, geo);
+        const int rc = check_launch("mlp stream gemm (ragged group keys)");
         return rc ? rc : 1;
     }
     if constexpr (AMODE == A_XYZ) hipLaunchKernelGGL((stream_kernel<AMODE, EPI, KB16, CK, WN, false>), grid, dim3(512), 0, st, p, geo);   // (no streamed operand: no asm ring)
@@ -959,6 +1009,11 @@ int stream_gemm_try(const GemmArgs &p, int amode, int epi, bool vec, hipStream_t
         geo.kgshift = s;
     }
     geo.n_units = (int)((p.M / 32) >> geo.ushift);
+    if (p.gm.keys) {      // ragged-group extremum epilogue (SG): 128 input channels, column blocks of 128 -- the compacted max layer 128 -> 256
+        if (!(amode == A_BNRELU && epi == EPI_STORE && geo.rows_dev && p.gm.seg && p.gm.sgn)) return why(13);
+        if (p.Kin == 128 && p.Nout % 128 == 0) return stream_go<A_BNRELU, EPI_STORE, 8, 4, false, 128, false, 128, false, true>(p, geo, st);
+        return why(14);
+    }
     if (amode == A_BNRELU && epi == EPI_STORE) return stream_pick<A_BNRELU, EPI_STORE>(p, geo, st);
     if (amode == A_BNRELU && epi == EPI_GMAX) return knob(KNOB_STREAM_ASM) ? stream_pick<A_BNRELU, EPI_GMAX>(p, geo, st) : 0;
     if (amode == A_BNRELU && epi == EPI_STORE_GMAX) return stream_pick<A_BNRELU, EPI_STORE_GMAX>(p, geo, st);

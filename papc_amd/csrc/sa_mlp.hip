@@ -33,6 +33,10 @@ int pfn_apply_impl(const float *features, const int32_t *num_voxels, const int32
 int pfn_bwd_sparse_impl(const float *features, const int32_t *num_voxels, const int32_t *coors, int P, int T, float vx, float vy, float x_offset, float y_offset,
                         const float *w, int C, const float *gout, const int32_t *argmax, const float *mean, const float *invstd, const float *scale,
                         const float *shift, float *partial, int zero_padded, papc_stream_t stream);
+// (bn_ops.hip: papc_bn_finalize_f32 with a buffer cleared by the same launch)
+int bn_finalize_clear(const float *stats_partial, int n_tiles, int64_t M, int C, const float *gamma, const float *beta, float eps, float momentum,
+                      float *mean, float *invstd, float *scale, float *shift, float *running_mean, float *running_var, void *clr, int64_t bytes,
+                      hipStream_t st);
 int pfn_bwd_fold_finalize(const float *partial, int n_chunks, float *sums, int64_t M, const float *w, int C, const double *gram, const float *mean,
                           const float *invstd, const float *scale, float *dgamma, float *dbeta, float *dw, int flags, unsigned *ticket, hipStream_t st);
 
@@ -64,6 +68,7 @@ struct FwdPtrs {
     int32_t *gbuf_i;                    // [2, G, c_L]
     float *P, *wfeat;                   // gather-add first layer: per-point products [B*N, c_0], feature block of its weight [c_0, D]
     double *gpart;                      // coordinates-only first layer: partial moments
+    unsigned long long *keys;           // compacted pooled stack: [G, c_L] extremum keys of the ragged groups (the last layer's forward -> the select kernel)
 };
 struct BwdPtrs {
     float *c12[PAPC_SA_MAX_LAYERS];     // [2, c_l]
@@ -91,6 +96,13 @@ static bool defer_fold(const papc_sa_grads &gr, const float *partial, int n_chun
 }
 static bool defer_room(const papc_sa_grads &gr, int n) { return gr.defer && gr.defer->jobs && gr.defer->count + n <= gr.defer->capacity; }
 static inline int cin_of(const papc_sa_plan &p, int l) { return l == 0 ? p.cin0 : p.d.cout[l - 1]; }
+// the widths of a compacted pooled stack's last layer have the ragged-group extremum epilogue (papc_mlp_seg_epi_ok's widths; no knob in
+// here: the scratch layout must not move between plan and call)
+static inline bool seg_epi_widths(const papc_sa_plan &p)
+{
+    const int L = p.d.n_layers;
+    return p.compact && p.d.pool && L >= 2 && cin_of(p, L - 1) == 128 && p.d.cout[L - 1] % 128 == 0;
+}
 
 // rows per dW chunk, at least 256 -- except the gather-add layer's dW_f = G^T feats over the B N source points: 64 (at 256 its 16 384 rows ran on 64
 // workgroups, a quarter of the chip, for 24 us: step 1.482 -> 1.464 ms; the same floor for every small-M launch cost config 3 0.03 ms)
@@ -151,6 +163,7 @@ static size_t layout_fwd(const papc_sa_plan &p, void *base, FwdPtrs &f)
     if (p.gmax) f.gbuf_i = c.take<int32_t>(2 * (size_t)G * p.d.cout[L - 1]);
     if (p.lin0) f.wfeat = c.take<float>((size_t)p.d.cout[0] * p.d.D);     // (P itself lives in `saved`: the backward reads it again)
     if (p.xyz1) f.gpart = c.take<double>((size_t)papc_xyz_parts(M) * 16 + 16);
+    if (seg_epi_widths(p)) f.keys = c.take<unsigned long long>((size_t)G * p.d.cout[L - 1]);
     return c.off;
 }
 
@@ -548,6 +561,12 @@ int papc_sa_mlp_fwd(const papc_sa_plan *plan, const papc_sa_io *io, papc_stream_
     int cmax = 0;
     for (int l = 0; l < L; ++l) cmax = std::max(cmax, d.cout[l]);
     const size_t stats_stride = (size_t)(std::max(parts, p.lin0 ? papc_lingather_parts(M) : 0) + R_c) * 2 * cmax;
+    // PAPC_SEG_EPI: the last layer's forward keeps the extremum of every ragged group as a packed key (64-bit integer atomic max, exact in any
+    // order) and papc_bn_relu_select_seg_f32 replaces papc_bn_relu_max_seg_f32's pass over the stored output; bit-identical results.  The
+    // key buffer lives in the caller's scratch, which may hold anything: it is cleared by the bn_finalize launch of layer L - 2 (bn_finalize_clear
+    // -- extra workgroups of a launch far below its floor, not a launch of its own).  That launch precedes the last layer's forward on this
+    // stream, and kernel boundaries on one stream order the clear ahead of the first atomic.
+    const bool seg_epi = seg_epi_widths(p) && !ev && knob(KNOB_SEG_EPI) && papc_mlp_seg_epi_ok(M, cin_of(p, L - 1), d.cout[L - 1]);
 
     const float *prev_y = nullptr, *prev_sc = nullptr, *prev_sh = nullptr;
     int cin = p.cin0;
@@ -601,6 +620,9 @@ int papc_sa_mlp_fwd(const papc_sa_plan *plan, const papc_sa_io *io, papc_stream_
             SA_CALL(papc_lingather_fwd_f32(s.P, &grp, d.B, ly.w, cin, d.xyz_first ? 0 : d.D, ly.b, cout, y, stats, st));
         } else if (l == 0) {
             SA_CALL(papc_mlp_gemm_f32(A_GROUP_, nullptr, 0, &grp, nullptr, nullptr, ly.w, ly.b, M, cin, cout, y, stats, gm_ref, st));
+        } else if (p.compact && seg_epi && l == L - 1) {
+            SA_CALL(papc_mlp_gemm_rows_keys_f32(prev_y, cin, prev_sc, prev_sh, ly.w, ly.b, M, cin, cout, y, stats, io->compact->rows,
+                                                wstats ? io->compact->wrow : nullptr, io->compact->seg_grp, ly.gamma, f.keys, st));
         } else if (p.compact) {
             SA_CALL(papc_mlp_gemm_rows_w_f32(A_BNRELU_, prev_y, cin, nullptr, prev_sc, prev_sh, ly.w, ly.b, M, cin, cout, y, stats, nullptr, io->compact->rows,
                                              wstats ? io->compact->wrow : nullptr, st));
@@ -612,12 +634,17 @@ int papc_sa_mlp_fwd(const papc_sa_plan *plan, const papc_sa_io *io, papc_stream_
             parts_l += R_c;
         }
         if (ev) SA_CALL(papc_bn_eval_consts_f32(ly.running_mean, ly.running_var, ly.gamma, ly.beta, d.eps, cout, cst, cst + cout, cst + 2 * cout, cst + 3 * cout, st));
+        else if (seg_epi && l == L - 2)
+            SA_CALL(bn_finalize_clear(stats, parts_l, M, cout, ly.gamma, ly.beta, d.eps, d.momentum, cst, cst + cout, cst + 2 * cout, cst + 3 * cout,
+                                      ly.running_mean, ly.running_var, f.keys, (int64_t)G * d.cout[L - 1] * 8, as_stream(st)));
         else SA_CALL(papc_bn_finalize_f32(stats, parts_l, M, cout, ly.gamma, ly.beta, d.eps, d.momentum, cst, cst + cout, cst + 2 * cout, cst + 3 * cout,
                                           ly.running_mean, ly.running_var, st));
         prev_y = y; prev_sc = cst + 2 * cout; prev_sh = cst + 3 * cout;
         cin = cout;
     }
     if (!d.pool) return papc_bn_relu_f32(prev_y, prev_sc, prev_sh, M, cin, io->out, st);
+    if (p.compact && seg_epi)
+        return papc_bn_relu_select_seg_f32(f.keys, prev_y, cin, io->compact->start, io->layer[L - 1].gamma, prev_sc, prev_sh, (int)G, io->out, s.argmax, s.gbuf_f, st);
     if (p.compact) return papc_bn_relu_max_seg_f32(prev_y, cin, io->compact->start, prev_sc, prev_sh, (int)G, io->out, s.argmax, s.gbuf_f, st);
     if (p.gmax) return papc_bn_select_max_f32(s.gbuf_f, s.gbuf_f + G * cin, f.gbuf_i, f.gbuf_i + G * cin, prev_sc, prev_sh, G, cin, io->out, s.argmax, st);
     return papc_bn_relu_max_f32(prev_y, prev_sc, prev_sh, G, d.K, cin, io->out, s.argmax, st);
