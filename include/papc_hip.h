@@ -471,6 +471,9 @@ typedef struct papc_sa_plan {
 typedef struct papc_sa_grads {
     const float *gout;
     float *dw[PAPC_SA_MAX_LAYERS], *db[PAPC_SA_MAX_LAYERS], *dgamma[PAPC_SA_MAX_LAYERS], *dbeta[PAPC_SA_MAX_LAYERS];
+    /* accumulate flags per layer (0: the buffer is overwritten, non-zero: the gradient is added to what it holds).  acc_w covers dw and db,
+     * acc_gb covers dgamma and dbeta -- in train AND eval mode (eval_bn).  Train mode: db is an exact zero (a bias under a batch norm), written
+     * only when acc_w is 0.  Eval mode: db = scale * (this pass's dbeta) is a real gradient and follows acc_w, whatever acc_gb says. */
     int32_t acc_w[PAPC_SA_MAX_LAYERS], acc_gb[PAPC_SA_MAX_LAYERS];
     const float *wt[PAPC_SA_MAX_LAYERS];
     float *grad_feats, *grad_x;

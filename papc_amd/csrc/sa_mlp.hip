@@ -463,6 +463,15 @@ __global__ void mul_vec_kernel(const float *__restrict__ a, const float *__restr
     if (i < n) out[i] = accumulate ? out[i] + a[i] * b[i] : a[i] * b[i];
 }
 
+__global__ void add_vec2_kernel(const float *__restrict__ a0, const float *__restrict__ a1, int n, float *__restrict__ o0, float *__restrict__ o1)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;      // (o0 / o1: either may be NULL -- a gradient the caller did not ask for)
+    if (i < n) {
+        if (o0) o0[i] += a0[i];
+        if (o1) o1[i] += a1[i];
+    }
+}
+
 }  // namespace papc
 
 using namespace papc;
@@ -659,6 +668,10 @@ int papc_sa_mlp_bwd(const papc_sa_plan *plan, const papc_sa_io *io, const papc_s
     const int64_t M = rows_of(d), G = (int64_t)d.B * d.S;
     const bool plain = d.input == PAPC_SA_IN_ROWS, ev = d.eval_bn != 0;
     if (p.planes) return planes_bwd(p, *io, *gr, st);
+    // (the eval-mode bias gradient and its accumulate fix-up sit in the generic dW branch below: the plans that leave the loop early are train-mode only)
+    PAPC_REQUIRE(!ev || !(p.lin0 || p.xyz1 || p.nostore || p.sparse_max || p.compact || p.gmax), PAPC_E_INVALID,
+                 "papc_sa_mlp_bwd: an eval_bn plan with a train-mode path set (lin0 %d xyz1 %d nostore %d sparse_max %d compact %d gmax %d)", p.lin0, p.xyz1,
+                 p.nostore, p.sparse_max, p.compact, p.gmax);
     SavedPtrs s; BwdPtrs b;
     layout_saved(p, io->saved, s);
     layout_bwd(p, io->scratch, b);
@@ -711,8 +724,12 @@ int papc_sa_mlp_bwd(const papc_sa_plan *plan, const papc_sa_io *io, const papc_s
         const int cout = d.cout[l], cin = cin_of(p, l);
         const float *cst = s.cst[l];
         float *c12 = b.c12[l];
-        const bool acc_w = gr->acc_w[l] != 0, acc_gb = gr->acc_gb[l] != 0 && !ev;
+        const bool acc_w = gr->acc_w[l] != 0, acc_gb = gr->acc_gb[l] != 0;
         float *dgamma = gr->dgamma[l] ? gr->dgamma[l] : b.tmp_gb, *dbeta = gr->dbeta[l] ? gr->dbeta[l] : b.tmp_gb + cmaxc;
+        // eval-mode norm with acc_gb: the bias gradient below is scale * THIS pass's dbeta, so the fresh pair goes to tmp_gb first and is added
+        // to the caller's buffers once db has read it (a NULL dgamma / dbeta is tmp_gb already and must not be accumulated into either)
+        const bool gb_tmp = ev && acc_gb && gr->db[l];
+        float *fgamma = gb_tmp ? b.tmp_gb : dgamma, *fbeta = gb_tmp ? b.tmp_gb + cmaxc : dbeta;
         PAPC_REQUIRE(gr->dw[l], PAPC_E_INVALID, "papc_sa_mlp_bwd: dw[%d] is NULL", l);
         papc_bwd_dy dy;
         memset(&dy, 0, sizeof(dy));
@@ -750,7 +767,7 @@ int papc_sa_mlp_bwd(const papc_sa_plan *plan, const papc_sa_io *io, const papc_s
                 SA_CALL(papc_bn_bwd_reduce_f32(dy.dz_mode, dy.dz_mode == PAPC_DZ_MAX ? ysel : dy.dz, dy.gout, dy.argmax, dy.K, dy.y, dy.mean, dy.invstd, dy.scale,
                                                dy.shift, M, cout, n_parts, b.red, st));
         } else { red = fused_red; red_parts = gemm_parts; }
-        SA_CALL(papc_bn_bwd_finalize_f32(red, red_parts, M, cout, dgamma, dbeta, c12, c12 + cout, (acc_gb ? 1 : 0) | (ev ? 2 : 0), st));
+        SA_CALL(papc_bn_bwd_finalize_f32(red, red_parts, M, cout, fgamma, fbeta, c12, c12 + cout, ((acc_gb && !gb_tmp) ? 1 : 0) | (ev ? 2 : 0), st));
         if (l == 0 && p.lin0) {
             // G[j] = sum of the dY rows that gathered point j (+ the xyz columns of dW, streamed); the D-wide products run on B*N rows
             const int64_t BN = (int64_t)d.B * d.N;
@@ -825,8 +842,12 @@ int papc_sa_mlp_bwd(const papc_sa_plan *plan, const papc_sa_io *io, const papc_s
                 j.n2 = want_db ? cout : 0; j.out2 = want_db ? gr->db[l] : nullptr;
             }
             if (ev && gr->db[l]) {     // no batch-mean term removes the bias direction: db = sum_m dy = scale * sum_m p
-                hipLaunchKernelGGL(mul_vec_kernel, dim3((unsigned)cdiv(cout, 256)), dim3(256), 0, as_stream(st), cst + 2 * cout, dbeta, cout, gr->db[l], acc_w ? 1 : 0);
+                hipLaunchKernelGGL(mul_vec_kernel, dim3((unsigned)cdiv(cout, 256)), dim3(256), 0, as_stream(st), cst + 2 * cout, fbeta, cout, gr->db[l], acc_w ? 1 : 0);
                 SA_CALL(check_launch("papc_sa_mlp_bwd (eval-mode bias gradient)"));
+                if (gb_tmp) {
+                    hipLaunchKernelGGL(add_vec2_kernel, dim3((unsigned)cdiv(cout, 256)), dim3(256), 0, as_stream(st), fgamma, fbeta, cout, gr->dgamma[l], gr->dbeta[l]);
+                    SA_CALL(check_launch("papc_sa_mlp_bwd (eval-mode dgamma / dbeta accumulate)"));
+                }
             }
         }
         // ---- dX

@@ -48,7 +48,13 @@ def level_literal(x, sel, w, b, gamma, beta, dim, running=None):
     return torch.max(y, dim=-1)[0], mean, var                                                     # :59
 
 
-def level(rows, sel, w, b, gamma, beta, B, dim, dec=None, running=None):
+def _count(tally, key, n, of):
+    if tally is not None:
+        tally[key] = tally.get(key, 0) + int(n)
+        tally["decisions"] = tally.get("decisions", 0) + int(of)
+
+
+def level(rows, sel, w, b, gamma, beta, B, dim, dec=None, running=None, tally=None):
     """The same level on point-major rows, the norm over the full [B*dim, 3F] conv output.  rows [B*dim, Cin] -> (out [B*dim/2, F], win, alive,
     mean [3F], var [3F], zhat [B*dim/2, F] of the picked rows): with dec = (win, alive) the kernel's decisions, else the reference's own (the
     first row of a pair on an exact tie)."""
@@ -68,31 +74,42 @@ def level(rows, sel, w, b, gamma, beta, B, dim, dec=None, running=None):
         t = torch.gather(t.view(B, dim, 3 * f), 1, p.view(B, dim, 1).expand(B, dim, 3 * f))       # the source point's row
         return torch.gather(t.view(B, dim, f, 3), 3, k.view(B, dim, 1, 1).expand(B, dim, f, 1)).view(B * dim // 2, 2, f)
     y = pick(a3)
+    r = torch.relu(y.detach())
     if dec is None:
-        r = torch.relu(y.detach())
         win = (r[:, 1] > r[:, 0]).to(torch.uint8)
         alive = torch.maximum(r[:, 0], r[:, 1]) > 0
     else:
         win, alive = dec
+        # pinned decisions that differ from the reference's own: a winner strictly below its pair's max (an exact tie has two own winners), and
+        # alive / dead of the pinned winner
+        rw = torch.gather(r, 1, win.long().view(-1, 1, f)).view(-1, f)
+        _count(tally, "winner_moves", (rw < torch.maximum(r[:, 0], r[:, 1])).sum(), rw.numel())
+        _count(tally, "alive_flips", (alive != (torch.gather(y.detach(), 1, win.long().view(-1, 1, f)).view(-1, f) > 0)).sum(), rw.numel())
     idx = win.long().view(-1, 1, f)
     picked = torch.gather(y, 1, idx).view(-1, f)
     zhat = torch.gather(pick(z3), 1, idx).view(-1, f)
     return torch.where(alive, picked, torch.zeros_like(picked)), win, alive, mean, var, zhat
 
 
-def _cbr(P, name, rows, mask, running):
+def _cbr(P, name, rows, mask, running, tally=None, export=None):
     """ConvBNReLU (kdunet.py:20-39) on rows [M, Cin]; mask: the kernel's ReLU decisions or None"""
     w = P[name + "._conv.weight"]
     y = rows @ w.view(w.shape[0], -1).t() + P[name + "._conv.bias"]
     run = None if running is None else (running[name + "._batch_norm.running_mean"], running[name + "._batch_norm.running_var"])
     y, mean, var = batch_norm(y, P[name + "._batch_norm.weight"], P[name + "._batch_norm.bias"], (0,), run)
+    if export is not None:
+        export.append(y.detach() > 0)
+    if mask is not None:
+        _count(tally, "relu_flips", (mask != (y.detach() > 0)).sum(), y.numel())
     return (torch.relu(y) if mask is None else torch.where(mask, y, torch.zeros_like(y))), mean, var
 
 
-def kdunet(P, x, sels, dec=None, up_dec=None, running=None):
+def kdunet(P, x, sels, dec=None, up_dec=None, running=None, tally=None, export=None):
     """P: {name: float64 tensor} under the model's parameter names, x [B, 3, 1024], sels: the first five split vectors ([dim_l] or [B, dim_l]),
     dec: five (win, alive) or None, up_dec: {(stack 1..5, layer 0..1): bool mask} (missing: the reference's own ReLU), running: None (train
-    mode) or {buffer name: float64 tensor} (eval mode) -> (logits [B, 1024, classes], {norm module name: (batch mean, batch var)})"""
+    mode) or {buffer name: float64 tensor} (eval mode) -> (logits [B, 1024, classes], {norm module name: (batch mean, batch var)}).  ``tally``: a dict that counts the pinned decisions which
+    differ from the reference's own (winner_moves, alive_flips, relu_flips, decisions); ``export``: a list that receives the reference's own
+    decisions in call order -- five (win, alive), then the up half's ReLU masks"""
     B = x.shape[0]
     up_dec = up_dec or {}
     stats = {}
@@ -103,8 +120,10 @@ def kdunet(P, x, sels, dec=None, up_dec=None, running=None):
         w = P[n + "._conv.weight"]
         shortcut.append(rows)
         run = None if running is None else (running[n + "._batch_norm.running_mean"], running[n + "._batch_norm.running_var"])
-        rows, _, _, mean, var, _ = level(rows, sels[i], w.view(w.shape[0], -1), P[n + "._conv.bias"], P[n + "._batch_norm.weight"],
-                                         P[n + "._batch_norm.bias"], B, dim, None if dec is None else dec[i], run)
+        rows, win, alive, mean, var, _ = level(rows, sels[i], w.view(w.shape[0], -1), P[n + "._conv.bias"], P[n + "._batch_norm.weight"],
+                                               P[n + "._batch_norm.bias"], B, dim, None if dec is None else dec[i], run, tally)
+        if export is not None:
+            export.append((win, alive))
         stats[n + "._batch_norm"] = (mean, var)
     npts = LEVELS[-1][0] // 2
     for i in range(5):
@@ -113,10 +132,10 @@ def kdunet(P, x, sels, dec=None, up_dec=None, running=None):
         npts *= 2
         rows = torch.cat([t.transpose(1, 2).reshape(B * npts, -1), shortcut[4 - i]], 1)           # :100 concat along channels, deconv first
         n = "upsample.doubleconv%d" % (i + 1)
-        rows, mean, var = _cbr(P, n + ".0", rows, up_dec.get((i + 1, 0)), running)
+        rows, mean, var = _cbr(P, n + ".0", rows, up_dec.get((i + 1, 0)), running, tally, export)
         stats[n + ".0._batch_norm"] = (mean, var)
         if i < 4:
-            rows, mean, var = _cbr(P, n + ".1", rows, up_dec.get((i + 1, 1)), running)
+            rows, mean, var = _cbr(P, n + ".1", rows, up_dec.get((i + 1, 1)), running, tally, export)
             stats[n + ".1._batch_norm"] = (mean, var)
         else:
             w = P[n + ".1.weight"]

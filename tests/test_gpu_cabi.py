@@ -35,8 +35,10 @@ def _sample(dev, B, N, S, K, radius, seed):
     return xyz, new_xyz, idx
 
 
-def _raw_stack(dev, B, N, S, K, D, chans, xyz, new_xyz, feats, idx, ws, gout, compact=None, want_feats_grad=False):
-    """one forward + backward of a stack through the three C entry points only; returns (out, grads per layer, grad_feats, plan, views)"""
+def _raw_stack(dev, B, N, S, K, D, chans, xyz, new_xyz, feats, idx, ws, gout, compact=None, want_feats_grad=False, running=None, acc=0, prefill=None, null_dgamma=False):
+    """one forward + backward of a stack through the three C entry points only; returns (out, grads per layer, grad_feats, plan, views).
+    ``running`` [(mean, var)] per layer: eval_bn = 1 on these statistics; ``acc``: the value of every acc_w / acc_gb flag; ``prefill``: what the
+    four gradient buffers of every layer hold before the call (a float, default: uninitialised); ``null_dgamma``: the caller asks for no dgamma"""
     lib = _lib.load()
     L = len(chans) - 1
     st = torch.cuda.current_stream().cuda_stream
@@ -45,7 +47,7 @@ def _raw_stack(dev, B, N, S, K, D, chans, xyz, new_xyz, feats, idx, ws, gout, co
     d.B, d.N, d.S, d.K, d.D, d.n_layers, d.cin = B, N, S, K, D, L, D + 3
     for l in range(L):
         d.cout[l] = chans[l + 1]
-    d.input, d.identity_rows, d.xyz_first, d.pool, d.eval_bn = 0, int(idx is None), 1, 1, 0
+    d.input, d.identity_rows, d.xyz_first, d.pool, d.eval_bn = 0, int(idx is None), 1, 1, int(running is not None)
     d.eps, d.momentum = 1e-5, 0.9
     io = SaIo()
     io.xyz, io.sb, io.sn, io.sc = xyz.data_ptr(), xyz.stride(0), xyz.stride(1), xyz.stride(2)
@@ -62,6 +64,9 @@ def _raw_stack(dev, B, N, S, K, D, chans, xyz, new_xyz, feats, idx, ws, gout, co
     io.consts3, io.consts3_ld = c3.data_ptr(), 1024
     for l in range(L):
         io.layer[l].w, io.layer[l].b, io.layer[l].gamma, io.layer[l].beta = (t.data_ptr() for t in par[l])
+        if running is not None:
+            keep.append(tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in running[l]))
+            io.layer[l].running_mean, io.layer[l].running_var = (t.data_ptr() for t in keep[-1])
     plan = SaPlan()
     _lib.check(lib.papc_sa_mlp_plan(ctypes.byref(d), ctypes.byref(io), ctypes.byref(plan)), "papc_sa_mlp_plan")
     G, Mrows = B * S, B * S * K
@@ -89,7 +94,13 @@ def _raw_stack(dev, B, N, S, K, D, chans, xyz, new_xyz, feats, idx, ws, gout, co
         cin = D + 3 if l == 0 else chans[l]
         t = [torch.empty(chans[l + 1], cin, device=dev), torch.empty(chans[l + 1], device=dev), torch.empty(chans[l + 1], device=dev),
              torch.empty(chans[l + 1], device=dev)]
+        if prefill is not None:
+            for j, x in enumerate(t):
+                x.fill_(prefill + 0.25 * j + l)
         g.dw[l], g.db[l], g.dgamma[l], g.dbeta[l] = (x.data_ptr() for x in t)
+        g.acc_w[l] = g.acc_gb[l] = acc
+        if null_dgamma:
+            g.dgamma[l] = None
         grads.append(t)
     gf = None
     if want_feats_grad:
@@ -140,6 +151,55 @@ def test_stack_through_raw_c_entry_points_vs_f64(dev, name, B, N, S, K, radius, 
         assert float(grads[l][1].abs().max()) <= 1e-4 * float(p64[l][0].grad.abs().max())      # bias under a train-mode BN: ~0
     if gf is not None:
         assert_close(gf.cpu().numpy(), f64.grad.cpu().numpy(), 2e-4, name + ": dfeats")
+
+
+def test_eval_stack_accumulate_flags_through_raw_c_entry_points(dev):
+    """eval_bn = 1 with acc_w = acc_gb = 1: all four gradient buffers of every layer hold prefill + the fresh gradient, where "fresh" is the
+    same call with the flags 0 (include/papc_hip.h, papc_sa_grads: acc_w covers dw and db, acc_gb covers dgamma and dbeta, in both modes;
+    db = scale * dbeta of THIS pass, so it must not read the caller's running dbeta)"""
+    B, N, S, K, D, chans = 3, 300, 20, 16, 5, [8, 32, 48, 20]
+    xyz, new_xyz, idx = _sample(dev, B, N, S, K, 0.3, 21)
+    rng = np.random.default_rng(4)
+    feats = torch.from_numpy(rng.normal(size=(B, N, D)).astype(np.float32)).to(dev)
+    ws = seeded_weights(chans, 77)
+    running = [((rng.normal(size=c) * 0.1).astype(np.float32), rng.uniform(0.5, 2.0, size=c).astype(np.float32)) for c in chans[1:]]
+    gout = torch.from_numpy(rng.normal(size=(B * S, chans[-1])).astype(np.float32)).to(dev)
+    out0, fresh, _, plan, (argmax, masks) = _raw_stack(dev, B, N, S, K, D, chans, xyz, new_xyz, feats, idx, ws, gout, running=running, acc=0, prefill=3.0)
+    assert plan.d.eval_bn == 1 and not (plan.lin0 or plan.xyz1 or plan.gmax or plan.nostore or plan.planes)
+    out1, accd, _, _, _ = _raw_stack(dev, B, N, S, K, D, chans, xyz, new_xyz, feats, idx, ws, gout, running=running, acc=1, prefill=3.0)
+    assert torch.equal(out0, out1)
+    # the fresh gradients themselves against float64 on the running statistics, routed through the kernels' own decisions
+    p64 = [[torch.from_numpy(a).to(dev).double().requires_grad_(True) for a in tup] for tup in ws]
+    rows = torch_ref.group(xyz.double(), new_xyz.double(), feats.double(), idx, True).reshape(B * S * K, D + 3)
+    run64 = [tuple(torch.from_numpy(a).to(dev).double() for a in r) for r in running]
+    ref, stats = torch_ref.stack_routed(rows, [tuple(t) for t in p64], K, 1e-5, argmax, out0 > 0, masks, running=run64)
+    # the cap on pinned decisions (tests/test_gpu_eval_backward.py): at most 0.1 % of the stack's decisions differ from float64's own.  (A float32
+    # CPU run of this twin, on the C oracle's sampling of the same clouds, differs from its float64 run in 0 of 79200.)
+    moved = stats["relu_flips"] + stats["winner_moves"] + stats["alive_flips"]
+    print("[decisions] eval stack via the C entry points: %d of %d differ from float64's own (%s)" % (moved, stats["decisions"], stats))
+    assert moved <= 1e-3 * stats["decisions"], (moved, stats)
+    assert_close(out0.cpu().numpy(), ref.detach().cpu().numpy(), 1e-5, "eval stack via the C entry points: forward")
+    ref.backward(gout.double())
+    bad = []
+    for l in range(len(chans) - 1):
+        for j, nm in enumerate(("w", "b", "gamma", "beta")):
+            pre = 3.0 + 0.25 * j + l
+            assert_close(fresh[l][j].cpu().numpy(), p64[l][j].grad.cpu().numpy(), 2e-4, "eval fresh d%s layer %d vs f64" % (nm, l))
+            # prefill + fresh is ONE fp32 add per element (2^-24 of the sum, the sum at most twice the larger operand: 1.2e-7 of that
+            # operand); the bar leaves room for a kernel that forms the sum in another association
+            want = pre + fresh[l][j].double()
+            err = float((accd[l][j].double() - want).abs().max())
+            scale = max(pre, float(fresh[l][j].abs().max()))
+            print("[accumulate] d%s layer %d: |acc - (prefill + fresh)| = %.2e of %.2e (bar 1e-6)" % (nm, l, err / scale, scale))
+            if err > 1e-6 * scale:
+                bad.append("d%s layer %d: %.3e of %.3e" % (nm, l, err, scale))
+    assert not bad, bad
+    # a caller that asks for no dgamma: dbeta and db still accumulate, and db is still scale * THIS pass's dbeta
+    _, part, _, _, _ = _raw_stack(dev, B, N, S, K, D, chans, xyz, new_xyz, feats, idx, ws, gout, running=running, acc=1, prefill=3.0, null_dgamma=True)
+    for l in range(len(chans) - 1):
+        for j, nm in ((0, "w"), (1, "b"), (3, "beta")):
+            assert torch.equal(part[l][j], accd[l][j]), "dgamma = NULL: d%s layer %d differs from the call that asked for all four" % (nm, l)
+        assert bool((part[l][2] == 3.0 + 0.25 * 2 + l).all()), "dgamma = NULL: the buffer that was not handed over changed"
 
 
 def test_group_all_stack_through_raw_c_entry_points_vs_oracle(dev):

@@ -1,0 +1,859 @@
+"""The eval-mode (frozen-norm) backward of every autograd node that carries a BatchNorm, held to float64.
+
+model.eval() gives each such node a second backward -- running statistics, no batch-mean terms, a conv bias gradient that is a real number
+instead of an exact zero -- and the plans take other kernels there (the A_GROUP first layer, the stored cin = 3 first layer,
+papc_bn_relu_max_f32 on 128-row groups: everything the train-mode plan replaces).  Frozen-norm fine-tuning and input gradients in eval mode
+are ordinary uses, so every gradient is compared with a float64 twin that normalises with the same running statistics and takes the kernels'
+own ReLU / max decisions (tests/torch_ref.stack_routed): the comparison measures arithmetic, and the number of pinned decisions that differ
+from float64's own is capped at 0.1 % of the stack's decisions, asserted and printed in every test that pins.
+
+Seeds: a float32 CPU run of each twin differs from its float64 run in at most a tenth of that cap (``f32_drift`` below, run on the CPU;
+the measured counts stand next to the seeds)."""
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import reference_np as R
+from papc_amd import _lib
+from papc_amd import mlp as M_
+from papc_amd.mlp import StackSpec, shared_mlp_max
+from papc_amd.synthetic import make_clouds, make_pillars, make_start_idx
+from tests import kdunet_ref, pointnet_ref, pointnet_seg_ref, torch_ref, voxnet_ref
+from tests.util import assert_close, kernel_decisions, seeded_weights
+
+pytestmark = pytest.mark.gpu
+
+REL = 1e-5           # tests/test_gpu_mlp.py: forwards
+GTOL = 2e-4          # tests/test_gpu_mlp.py: gradients
+CAP = 1e-3           # pinned decisions that differ from float64's own: at most 0.1 % of the stack's decisions
+EPS = 1e-5
+
+
+def _np(t):
+    return t.detach().double().cpu().numpy()
+
+
+def _cap(stats, what):
+    moved = stats["relu_flips"] + stats["winner_moves"] + stats["alive_flips"]
+    print("[decisions] %s: %d of %d differ from float64's own (%s); cap %d" % (what, moved, stats["decisions"], {k: v for k, v in stats.items() if k != "decisions"},
+                                                                               int(CAP * stats["decisions"])))
+    assert moved <= CAP * stats["decisions"], "%s: %d pinned decisions differ from float64's own, cap %.0f" % (what, moved, CAP * stats["decisions"])
+    return moved
+
+
+def _running(c, rng):
+    """running statistics away from (0, 1), as the eval tests of the models seed them: mean 0.1 N(0, 1), var U(0.5, 2)"""
+    return (rng.normal(size=c) * 0.1).astype(np.float32), rng.uniform(0.5, 2.0, size=c).astype(np.float32)
+
+
+EDGE = (0, 1, 2, 3)
+
+
+def _edge_channels(g, rm, rv):
+    """four edge channels per layer: gamma < 0, gamma == 0, running_var == 0, running_mean large against the activations"""
+    g[0] = -abs(g[0]) - 0.25
+    g[1] = 0.0
+    rv[2] = 0.0
+    rm[3] = 10.0
+
+
+def close_split(got, ref, bar, what, rows=(), cols=()):
+    """assert_close with the edge channels taken off the ordinary channels' scale.  A channel with running_var == 0 has 1 / sigma = 316 and one
+    with running_mean = 10 activations of 10, and assert_close reads both of its bars on max|ref| of what it is given: in one call the bar would
+    bind the outlier alone.  So every edge row (an edge OUTPUT channel of the layer), every edge column (an edge channel of the layer below as
+    this layer's INPUT) and the block where the two cross is a piece of its own; a piece whose max|ref| does not exceed the ordinary block's joins
+    it (it is ordinary in size), a larger one is held to the bar on its own scale.  The split is decided by the float64 reference alone."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    if ref.ndim == 1:
+        got, ref = got[:, None], ref[:, None]
+    nr, nc = ref.shape
+    rmask, cmask = np.zeros(nr, bool), np.zeros(nc, bool)
+    rmask[list(rows)] = True
+    cmask[list(cols)] = True
+    pieces = [(" [edge row %d]" % r, np.ix_(np.arange(nr) == r, ~cmask)) for r in rows]
+    pieces += [(" [edge column %d]" % c, np.ix_(~rmask, np.arange(nc) == c)) for c in cols]
+    if len(rows) and len(cols):
+        pieces.append((" [edge rows x edge columns]", np.ix_(rmask, cmask)))
+    ordinary = np.ix_(~rmask, ~cmask)
+    og, orf = [got[ordinary].ravel()], [ref[ordinary].ravel()]
+    scale = float(np.abs(orf[0]).max())
+    for tag, ix in pieces:
+        if float(np.abs(ref[ix]).max()) <= scale:
+            og.append(got[ix].ravel())
+            orf.append(ref[ix].ravel())
+        else:
+            assert_close(got[ix], ref[ix], bar, what + tag)
+    return assert_close(np.concatenate(og), np.concatenate(orf), bar, what + (" [ordinary channels]" if (len(rows) or len(cols)) else ""))
+
+
+# ---- the shared-MLP stack ---------------------------------------------------------------------------------------------------------------
+# name: (B, N, S, K, D, widths, xyz_first, form, weight seed).  Every case runs twice: with the four edge channels in every layer, and without
+# them -- the input gradient sums over ALL channels of the first layer, so with a 316-fold channel in the stack it says nothing about the
+# others; the run without edge channels holds dfeats / dx_rows (and everything else) of ordinary channels to the bar.
+# Float32-vs-float64 decision drift of the twin on the CPU (f32_drift), with edge channels:
+#   a 0 of 147456, b 0 of 40960, b_msg 0 of 40960, c 0 of 139264, d 0 of 16896, e 0 of 50176, f 0 of 32768, g 0 of 230400
+# without: the same eight counts, 0 of each
+STACK_CASES = {
+    "a": (2, 256, 32, 16, 0, [64, 64, 128], True, "grouped", 40),         # grouped with idx; the stored cin = 3 first layer
+    "b": (2, 256, 32, 16, 16, [32, 64], True, "grouped", 41),             # feats.requires_grad, coordinates first
+    "b_msg": (2, 256, 32, 16, 16, [32, 64], False, "grouped", 41),        # ... MSG channel order
+    "c": (2, 256, 32, 16, 128, [128, 64], True, "grouped", 42),           # wide A_GROUP, scatter dX
+    "d": (2, 128, 1, 128, 64, [64, 128], True, "group_all", 43),          # identity rows, idx = None: the planes path's shape in train
+    "e": (2, 128, 1, 128, 64, [64, 128, 256], True, "rows", 44),          # plain rows [2 * 128, 64], pooled; x_rows.requires_grad
+    "f": (2, 128, 1, 128, 3, [64, 64], True, "rows_nopool", 45),          # plain rows [2 * 128, 3], pool = False
+    "g": (1, 3600, 3600, 1, 9, [64], True, "pfn_rows", 46),               # [120 * 30, 9], pool = False, one layer, zero bias without a gradient
+}
+
+
+def stack_case(name, edges=True):
+    """host arrays of one case: everything the kernels and the twin read, from numpy generators and the C oracle's sampling"""
+    B, N, S, K, D, widths, xyz_first, form, seed = STACK_CASES[name]
+    rng = np.random.default_rng(100 + seed)
+    c = {"name": name, "edges": bool(edges), "B": B, "N": N, "S": S, "K": K, "D": D, "widths": widths, "xyz_first": xyz_first, "form": form, "pool": form not in ("rows_nopool", "pfn_rows"),
+         "eps": 1e-3 if form == "pfn_rows" else EPS, "xyz": None, "new_xyz": None, "idx": None, "feats": None, "x_rows": None}
+    if form in ("grouped", "group_all"):
+        xyz = np.ascontiguousarray(make_clouds(B, N, 31 + N).transpose(0, 2, 1))
+        c["xyz"] = xyz
+        if form == "grouped":
+            fps = R.farthest_point_sample(xyz, S, make_start_idx(B, N, 1))
+            c["new_xyz"] = np.ascontiguousarray(R.index_points(xyz, fps)).astype(np.float32)
+            c["idx"] = R.query_ball_point(0.3, K, xyz, c["new_xyz"]).astype(np.int32)
+        else:
+            c["new_xyz"] = np.zeros((B, 1, 3), np.float32)
+        c["feats"] = rng.normal(size=(B, N, D)).astype(np.float32) if D else None
+        cin = D + 3
+    else:
+        cin = D
+        c["x_rows"] = rng.normal(size=(B * S * K, cin)).astype(np.float32)
+    ws = seeded_weights([cin] + widths, seed)
+    c["ws"], c["running"] = [], []
+    for (w, b, g, bt) in ws:
+        rm, rv = _running(len(g), rng)
+        g = g.copy()
+        if edges:
+            _edge_channels(g, rm, rv)
+        if form == "pfn_rows":
+            b = np.zeros_like(b)
+        c["ws"].append((w, b, g, bt))
+        c["running"].append((rm, rv))
+    c["gout"] = rng.normal(size=(B * S if c["pool"] else B * S * K, widths[-1])).astype(np.float32)
+    return c
+
+
+def stack_twin(c, dev, dtype, dec):
+    """the twin at ``dtype`` on ``dev``: -> (out, stats, leaves) with leaves = {"p": [[w, b, gamma, beta]], "feats", "x_rows"};
+    dec = (argmax, alive, masks) pinned, or "own": the chain's own decisions at this precision (returned as stats["own"])"""
+    t = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+    leaf = lambda a: t(a).to(dtype).requires_grad_(True)      # noqa: E731
+    p = [[leaf(a) for a in tup] for tup in c["ws"]]
+    running = [(t(rm).to(dtype), t(rv).to(dtype)) for rm, rv in c["running"]]
+    feats = leaf(c["feats"]) if c["feats"] is not None else None
+    x_rows = leaf(c["x_rows"]) if c["x_rows"] is not None else None
+    B, N, S, K = c["B"], c["N"], c["S"], c["K"]
+    if x_rows is not None:
+        rows = x_rows
+    else:
+        idx = t(c["idx"]) if c["idx"] is not None else torch.arange(N, device=dev).view(1, 1, N).expand(B, 1, N)
+        rows = torch_ref.group(t(c["xyz"]).to(dtype), t(c["new_xyz"]).to(dtype), feats, idx, c["xyz_first"]).reshape(B * S * K, -1)
+    params = [tuple(q) for q in p]
+    Kp = K if c["pool"] else 1
+    own = None
+    if isinstance(dec, str):
+        own = dec = torch_ref.own_decisions(rows.detach(), [tuple(a.detach() for a in q) for q in params], Kp, c["eps"], running)
+    argmax, alive, masks = dec
+    if not c["pool"]:
+        argmax = torch.zeros(rows.shape[0], c["widths"][-1], dtype=torch.long, device=dev)
+    out, stats = torch_ref.stack_routed(rows, params, Kp, c["eps"], argmax, alive, masks, running=running)
+    stats["own"] = own
+    return out, stats, {"p": p, "feats": feats, "x_rows": x_rows}
+
+
+def f32_drift(name, edges=True):
+    """CPU only: the decisions of a float32 run of the twin, pinned into its float64 run -> (differing, of)"""
+    c = stack_case(name, edges)
+    cpu = torch.device("cpu")
+    _, s32, _ = stack_twin(c, cpu, torch.float32, "own")
+    _, s64, _ = stack_twin(c, cpu, torch.float64, s32["own"])
+    return s64["relu_flips"] + s64["winner_moves"] + s64["alive_flips"], s64["decisions"]
+
+
+def _run_stack(c, dev, py_orch, monkeypatch):
+    """one eval-mode forward + backward of the HIP stack -> dict of results"""
+    monkeypatch.setattr(M_, "_PY_ORCH", py_orch)
+    t = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+    params = []
+    for (w, b, g, bt) in c["ws"]:
+        params += [t(a).requires_grad_(True) for a in (w, b, g, bt)]
+    if c["form"] == "pfn_rows":
+        params[1] = torch.zeros(c["widths"][0], device=dev)       # as PFNLayer.activations passes it: zeros, no gradient asked
+    bufs = [(t(rm), t(rv)) for rm, rv in c["running"]]
+    before = [(a.clone(), b.clone()) for a, b in bufs]
+    feats = t(c["feats"])
+    x_rows = t(c["x_rows"])
+    if feats is not None:
+        feats.requires_grad_(True)
+    if x_rows is not None and c["form"] == "rows":
+        x_rows.requires_grad_(True)
+    spec = StackSpec(c["B"], c["N"], c["S"], c["K"], c["D"] if x_rows is None else 0, c["xyz_first"], eps=c["eps"], pool=c["pool"])
+    spec.eval_bn = True
+    out = shared_mlp_max(spec, bufs, t(c["xyz"]), t(c["new_xyz"]), feats, t(c["idx"]), params, x_rows=x_rows)
+    node = type(out.grad_fn).__name__
+    assert node == ("SharedMLPMaxBackward" if py_orch else "SharedMLPStackBackward"), node       # the row kernels, never PlanesMLPMax
+    if not py_orch:
+        fn = out.grad_fn
+        assert not (fn.planes or fn.lin0 or fn.xyz1 or fn.nostore), "an eval stack takes none of the train-mode plans"
+    assert spec.grad_targets is None
+    dec = kernel_decisions(out)
+    out.backward(t(c["gout"]))
+    torch.cuda.synchronize()
+    for (a, b), (a0, b0) in zip(bufs, before):
+        assert torch.equal(a, a0) and torch.equal(b, b0), "eval mode moved the running statistics"
+    return {"out": out.detach(), "grads": [p.grad for p in params], "dfeats": None if feats is None else feats.grad,
+            "dx_rows": None if x_rows is None else x_rows.grad, "dec": dec}
+
+
+@pytest.mark.parametrize("edges", [True, False], ids=["edge_channels", "plain"])
+@pytest.mark.parametrize("name", sorted(STACK_CASES))
+def test_stack_eval_backward_vs_f64_both_orchestrations(dev, monkeypatch, name, edges):
+    """mlp.shared_mlp_max with spec.eval_bn under the library's orchestration (stack.SharedMLPStack) and the Python launch sequence
+    (mlp.SharedMLPMax): bit-identical to each other where no float atomics run, each held to float64 -- the conv bias gradient too.
+    With edge channels every comparison is split by channel (close_split); without them every tensor is ordinary throughout."""
+    c = stack_case(name, edges)
+    L = len(c["widths"])
+    E = EDGE if edges else ()
+    res = {po: _run_stack(c, dev, po, monkeypatch) for po in (False, True)}
+    lib_, py = res[False], res[True]
+    assert torch.equal(lib_["out"], py["out"]), "forward differs between the orchestrations"
+    for i, (a, b) in enumerate(zip(lib_["grads"], py["grads"])):
+        assert (a is None) == (b is None), i
+        assert a is None or torch.equal(a, b), "gradient %d (layer %d, %s) differs between the orchestrations" % (i, i // 4, "w b gamma beta".split()[i % 4])
+    if lib_["dx_rows"] is not None:
+        assert torch.equal(lib_["dx_rows"], py["dx_rows"])
+    if lib_["dfeats"] is not None and c["idx"] is None:
+        # identity rows: the scatter epilogue adds each dX entry ONCE onto a zeroed buffer -- an atomic, but nothing to reorder
+        assert torch.equal(lib_["dfeats"], py["dfeats"])
+    elif lib_["dfeats"] is not None:      # the scatter dX adds with float atomics: same terms, run-dependent order
+        assert float((lib_["dfeats"] - py["dfeats"]).abs().max()) <= 1e-5 * float(lib_["dfeats"].abs().max())
+    for po, r in res.items():
+        tag = "%s%s %s" % (name, "" if edges else " plain", "python" if po else "library")
+        argmax, alive, masks = r["dec"]
+        ref, stats, leaves = stack_twin(c, dev, torch.float64, (argmax, alive, masks))
+        _cap(stats, tag)
+        close_split(_np(r["out"]), _np(ref), REL, tag + ": forward", cols=E)
+        ref.backward(torch.from_numpy(c["gout"]).to(dev).double())
+        for l in range(L):
+            for j, nm in enumerate(["w", "b", "gamma", "beta"]):
+                got = r["grads"][4 * l + j]
+                if got is None and c["form"] == "pfn_rows" and j == 1:
+                    continue                # (the zero bias asked for no gradient)
+                # db = scale * sum p in eval: dbeta's relative error plus one rounding, so the same bar -- not "~ 0"
+                close_split(_np(got), _np(leaves["p"][l][j].grad), GTOL, "%s: d%s layer %d" % (tag, nm, l), rows=E, cols=E if (j == 0 and l > 0) else ())
+        if r["dfeats"] is not None:
+            assert_close(_np(r["dfeats"]), _np(leaves["feats"].grad), GTOL, tag + ": dfeats")
+        if r["dx_rows"] is not None:
+            assert_close(_np(r["dx_rows"]), _np(leaves["x_rows"].grad), GTOL, tag + ": dx_rows")
+    assert (lib_["dfeats"] is not None) == (c["feats"] is not None) and (lib_["dx_rows"] is not None) == (c["form"] == "rows")
+
+
+def test_flat_params_in_eval_go_through_autograd_and_accumulate(dev, monkeypatch):
+    """distributed.FlatParams opts every parameter in to in-place gradients; an eval-mode stack hands them all to autograd instead
+    (grad_targets is None), and two backward passes leave exactly twice the first pass's .grad"""
+    import papc_amd.models as MD
+    from papc_amd.distributed import FlatParams
+    from papc_amd.models import PointNet_Basic_Clas
+    B, N = 2, 128
+    torch.manual_seed(3)
+    m = PointNet_Basic_Clas(16).to(dev)          # (the FC head takes the stack's 1024 channels)
+    rng = np.random.default_rng(5)
+    with torch.no_grad():
+        for bn in m.bns:
+            rm, rv = _running(bn.num_features, rng)
+            bn.running_mean.copy_(torch.from_numpy(rm))
+            bn.running_var.copy_(torch.from_numpy(rv))
+    flat = FlatParams(m)
+    m.eval()
+    specs = []
+    inner = MD.shared_mlp_max
+
+    def rec(spec, *a, **k):
+        out = inner(spec, *a, **k)
+        specs.append(spec)
+        return out
+    monkeypatch.setattr(MD, "shared_mlp_max", rec)
+    before = {k: v.clone() for k, v in m.state_dict().items()}
+    x = torch.from_numpy(rng.normal(size=(B, 3, N)).astype(np.float32)).to(dev)
+    gout = torch.from_numpy(rng.normal(size=(B, 16)).astype(np.float32)).to(dev)
+    fired = set()
+    stack_params = {n: p for n, p in m.named_parameters() if n.startswith(("convs.", "bns."))}
+    for n, p in stack_params.items():
+        assert getattr(p, "_papc_inplace_grad", False), n
+        p.register_hook(lambda g_, n=n: fired.add(n) if g_ is not None else None)
+    flat.grad.zero_()
+    m(x).backward(gout)
+    torch.cuda.synchronize()
+    assert len(specs) == 1 and specs[0].eval_bn and specs[0].grad_targets is None
+    assert fired == set(stack_params), "stack gradients that did not go through autograd: %s" % sorted(set(stack_params) - fired)
+    first = {n: p.grad.clone() for n, p in stack_params.items()}
+    assert all(float(g.abs().max()) > 0 for g in first.values())
+    m(x).backward(gout)
+    torch.cuda.synchronize()
+    for n, p in stack_params.items():
+        assert torch.equal(p.grad, 2.0 * first[n]), n
+    for k, v in m.state_dict().items():
+        assert torch.equal(v, before[k]), k
+
+
+# ---- segment._CloudConcatBnRelu -----------------------------------------------------------------------------------------------------------
+SEG_BAR = 2e-4       # tests/test_gpu_pointnet_seg.py
+# float32-vs-float64 drift of the twin's ReLU decisions on the CPU (concat_f32_drift): cg = 64: 0 of 196608, cg = 128: 0 of 196608, with the
+# edge channels and without
+
+
+def concat_case(cg, edges=True, seed=51):
+    B, N, cp, cout = 3, 128, 64, 512
+    rng = np.random.default_rng(seed + cg)
+    w, b, g, bt = seeded_weights([cp + cg, cout], seed)[0]
+    rm, rv = _running(cout, rng)
+    g = g.copy()
+    if edges:
+        _edge_channels(g, rm, rv)
+    return {"B": B, "N": N, "cp": cp, "cg": cg, "cout": cout, "x": rng.normal(size=(B * N, cp)).astype(np.float32),
+            "g": np.maximum(rng.normal(size=(B, cg)), 0.0).astype(np.float32), "ws": (w, b, g, bt), "running": (rm, rv),
+            "gout": rng.normal(size=(B * N, cout)).astype(np.float32)}
+
+
+def concat_twin(c, dev, dtype, alive):
+    """relu(bn_running(conv(concat([x, tile(g, N)])))) at ``dtype``; alive: the pinned ReLU mask, or None for the chain's own (returned)"""
+    leaf = lambda a: torch.from_numpy(a).to(dev).to(dtype).requires_grad_(True)      # noqa: E731
+    x, g = leaf(c["x"]), leaf(c["g"])
+    p = [leaf(a) for a in c["ws"]]
+    running = [tuple(torch.from_numpy(a).to(dev).to(dtype) for a in c["running"])]
+    rows = torch.cat([x, g.repeat_interleave(c["N"], 0)], 1)
+    if alive is None:
+        alive = torch_ref.own_decisions(rows.detach(), [tuple(a.detach() for a in p)], 1, EPS, running)[1]
+    am = torch.zeros(rows.shape[0], c["cout"], dtype=torch.long, device=dev)
+    out, stats = torch_ref.stack_routed(rows, [tuple(p)], 1, EPS, am, alive, None, running=running)
+    return out, stats, alive, {"x": x, "g": g, "p": p}
+
+
+def concat_f32_drift(cg, edges=True):
+    c = concat_case(cg, edges)
+    cpu = torch.device("cpu")
+    a32 = concat_twin(c, cpu, torch.float32, None)[2]
+    s = concat_twin(c, cpu, torch.float64, a32)[1]
+    return s["relu_flips"] + s["winner_moves"] + s["alive_flips"], s["decisions"]
+
+
+@pytest.mark.parametrize("edges", [True, False], ids=["edge_channels", "plain"])
+@pytest.mark.parametrize("path", ["kernel", "materialised"])
+@pytest.mark.parametrize("cg", [64, 128])
+def test_cloud_concat_eval_backward_vs_f64(dev, monkeypatch, cg, path, edges):
+    """seg_net[0..2] with training=False on csrc/cloud_concat.hip and on its PAPC_SEG_CONCAT=0 twin (the materialised concat on the stack):
+    z, dx, dg, dw, db, dgamma, dbeta -- db is no longer zero.  With the edge channels the per-channel tensors are split by channel
+    (close_split); dx and dg sum over all 512 channels, so the run without edge channels is the one that holds them for ordinary channels."""
+    import papc_amd.segment as S
+    monkeypatch.setattr(S, "_SEG_CONCAT", path == "kernel")
+    c = concat_case(cg, edges)
+    E = EDGE if edges else ()
+    w, b, g, bt = c["ws"]
+    conv = torch.nn.Conv1d(c["cp"] + cg, c["cout"], 1).to(dev)
+    bn = torch.nn.BatchNorm1d(c["cout"], eps=EPS).to(dev)
+    with torch.no_grad():
+        conv.weight.copy_(torch.from_numpy(w).view(conv.weight.shape))
+        conv.bias.copy_(torch.from_numpy(b))
+        bn.weight.copy_(torch.from_numpy(g))
+        bn.bias.copy_(torch.from_numpy(bt))
+        bn.running_mean.copy_(torch.from_numpy(c["running"][0]))
+        bn.running_var.copy_(torch.from_numpy(c["running"][1]))
+    before = {k: v.clone() for k, v in bn.state_dict().items()}
+    x = torch.from_numpy(c["x"]).to(dev).requires_grad_(True)
+    gf = torch.from_numpy(c["g"]).to(dev).requires_grad_(True)
+    z = S.cloud_concat_bn_relu(x, gf, conv, bn, c["N"], False)
+    node = type(z.grad_fn).__name__
+    assert (node == "_CloudConcatBnReluBackward") == (path == "kernel"), node
+    ref, stats, _, leaves = concat_twin(c, dev, torch.float64, z.detach() > 0)
+    tag = "concat eval %s cg=%d%s" % (path, cg, "" if edges else " plain")
+    _cap(stats, tag)
+    close_split(_np(z), _np(ref), SEG_BAR, tag + ": z", cols=E)
+    z.backward(torch.from_numpy(c["gout"]).to(dev))
+    ref.backward(torch.from_numpy(c["gout"]).to(dev).double())
+    pw, pb, pg, pbt = leaves["p"]
+    for nm, got, want in (("dx", x.grad, leaves["x"].grad), ("dg", gf.grad, leaves["g"].grad), ("dw", conv.weight.grad.view(c["cout"], -1), pw.grad),
+                          ("db", conv.bias.grad, pb.grad), ("dgamma", bn.weight.grad, pg.grad), ("dbeta", bn.bias.grad, pbt.grad)):
+        close_split(_np(got), _np(want), SEG_BAR, "%s: %s" % (tag, nm), rows=() if nm in ("dx", "dg") else E)
+    for k, v in bn.state_dict().items():
+        assert torch.equal(v, before[k]), k
+
+
+# ---- kdnet.kdconv_bn ----------------------------------------------------------------------------------------------------------------------
+KD_BAR = 2e-4        # tests/test_gpu_kdunet.py
+KD_NODE_CASES = [(5, 16, 64, 96), (3, 64, 32, 64), (2, 1024, 3, 32)]     # (B, dim, Cin, F): the eval node test's own shape; Cin = 32 against 3F = 192; the Cin = 3 kernels
+
+
+def _kd_node(dev, B, dim, cin, f, seed=13):
+    from tests.test_gpu_kdunet import _level_params, _modules
+    g = torch.Generator().manual_seed(seed + dim)
+    x = torch.randn(B * dim, cin, generator=g)
+    w, b, gamma, beta, rmean, rvar = _level_params(cin, f, g)
+    sel = torch.randint(0, 3, (B, dim), generator=g)
+    gout = torch.randn(B * dim // 2, f, generator=g)
+    conv, bn = _modules(dev, cin, f, w, b, gamma, beta, rmean, rvar)
+    return x, (w, b, gamma, beta, rmean, rvar), sel, gout, conv, bn
+
+
+@pytest.mark.parametrize("B,dim,cin,f", KD_NODE_CASES)
+def test_kdconv_bn_eval_backward_vs_f64_and_inplace_accumulates(dev, monkeypatch, B, dim, cin, f):
+    """kdnet.kdconv_bn with training=False: dx, dw, dbias, dgamma, dbeta against float64 on the running statistics; then with FlatParams
+    in-place targets, where a second backward pass takes the accumulate branch of every gradient (dbias has one of its own in eval)"""
+    from papc_amd import kdnet
+    from papc_amd.distributed import FlatParams
+    monkeypatch.setattr(kdnet, "_KDCONV", True)
+    x, (w, b, gamma, beta, rmean, rvar), sel, gout, conv, bn = _kd_node(dev, B, dim, cin, f)
+    seld = sel.int().to(dev)
+    xd = x.to(dev).requires_grad_(True)
+    out = kdnet.kdconv_bn(xd, seld, conv, bn, B, dim, False)
+    assert type(out.grad_fn).__name__ == "_KDConvBNBackward"
+    leaf = lambda t: t.double().requires_grad_(True)      # noqa: E731
+    x64, w64, b64, ga64, be64 = leaf(x), leaf(w), leaf(b), leaf(gamma), leaf(beta)
+    dec = (out.grad_fn.saved_tensors[5].cpu(), (out.detach() > 0).cpu())
+    own = kdunet_ref.level(x64.detach(), sel.numpy(), w64.detach(), b64.detach(), ga64.detach(), be64.detach(), B, dim, running=(rmean.double(), rvar.double()))
+    pinned = kdunet_ref.level(x64, sel.numpy(), w64, b64, ga64, be64, B, dim, dec=dec, running=(rmean.double(), rvar.double()))
+    # decisions: the pair winner where the float64 pair does not tie, and alive / dead
+    y_own = own[0]
+    moved = int(((dec[0] != own[1]) & (pinned[0].detach() != y_own)).sum()) + int((dec[1] != own[2]).sum())
+    tag = "kdconv_bn eval B=%d dim=%d Cin=%d F=%d" % (B, dim, cin, f)
+    _cap({"relu_flips": 0, "winner_moves": moved, "alive_flips": 0, "decisions": 2 * out.numel()}, tag)
+    assert_close(_np(out), _np(pinned[0]), KD_BAR, tag + ": out")
+    out.backward(gout.to(dev))
+    pinned[0].backward(gout.double())
+    want = {"dW": w64.grad, "d bias": b64.grad, "dgamma": ga64.grad, "dbeta": be64.grad}
+    for name, got, ref in (("dX", xd.grad, x64.grad), ("dW", conv.weight.grad.view(3 * f, cin), w64.grad), ("d bias", conv.bias.grad, b64.grad),
+                           ("dgamma", bn.weight.grad, ga64.grad), ("dbeta", bn.bias.grad, be64.grad)):
+        assert_close(_np(got), _np(ref), KD_BAR, "%s: %s" % (tag, name))
+    assert torch.equal(bn.running_mean.cpu(), rmean) and torch.equal(bn.running_var.cpu(), rvar) and int(bn.num_batches_tracked) == 0
+    # in-place targets
+    _, _, _, _, conv2, bn2 = _kd_node(dev, B, dim, cin, f)
+    box = torch.nn.ModuleList([conv2, bn2])
+    flat = FlatParams(box)
+    flat.grad.zero_()
+    fired = []
+    for p in box.parameters():
+        p.register_hook(lambda g_: fired.append(1) if g_ is not None else None)
+    kdnet.kdconv_bn(x.to(dev), seld, conv2, bn2, B, dim, False).backward(gout.to(dev))
+    torch.cuda.synchronize()
+    assert not fired, "the in-place targets were not taken"
+    first = {"dW": conv2.weight.grad.clone().view(3 * f, cin), "d bias": conv2.bias.grad.clone(), "dgamma": bn2.weight.grad.clone(), "dbeta": bn2.bias.grad.clone()}
+    for name, got in first.items():
+        assert_close(_np(got), _np(want[name]), KD_BAR, "%s: in-place %s" % (tag, name))
+    kdnet.kdconv_bn(x.to(dev), seld, conv2, bn2, B, dim, False).backward(gout.to(dev))
+    torch.cuda.synchronize()
+    second = {"dW": conv2.weight.grad.view(3 * f, cin), "d bias": conv2.bias.grad, "dgamma": bn2.weight.grad, "dbeta": bn2.bias.grad}
+    for name, got in second.items():
+        assert torch.equal(got, 2.0 * first[name]), "%s: two backward passes are not twice the first (%s)" % (tag, name)
+
+
+# ---- PillarFeatureNet ---------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("inplace", [False, True])
+@pytest.mark.parametrize("filters", [(64,), (64, 128)])
+def test_pfn_eval_backward_vs_f64(dev, filters, inplace):
+    """PillarFeatureNet in eval with grad enabled: dW, dgamma, dbeta of every layer against float64 on the running statistics -- fresh tensors
+    (papc_pfn_bwd flags = 1) and FlatParams in-place targets (flags = 3 on the fused single layer; the two-layer net's stacks hand their
+    gradients to autograd in eval).  The running statistics stay."""
+    from papc_amd.distributed import FlatParams
+    from papc_amd.pillars import PillarFeatureNet
+    from tests.test_gpu_pfn import _torch_pfn_layer, _weights
+    P, T = 120, 30
+    voxels, nump, coors = make_pillars(P=P, T=T, seed=4)
+    vs, pr = (0.16, 0.16, 4), (0, -39.68, -3, 69.12, 39.68, 1)
+    net = PillarFeatureNet(num_filters=filters, voxel_size=vs, pc_range=pr).to(dev)
+    rng = np.random.default_rng(17)
+    cins = [9] + [filters[0]] * (len(filters) - 1)
+    with torch.no_grad():
+        for i, lay in enumerate(net.pfn_layers):
+            w, g, b = _weights(lay.units, cins[i], 20 + i)
+            lay.linear.weight.copy_(torch.from_numpy(w))
+            lay.norm.weight.copy_(torch.from_numpy(g))
+            lay.norm.bias.copy_(torch.from_numpy(b))
+            rm, rv = _running(lay.units, rng)
+            lay.norm.running_mean.copy_(torch.from_numpy(rm))
+            lay.norm.running_var.copy_(torch.from_numpy(rv))
+    flat = FlatParams(net) if inplace else None
+    net.eval()
+    fired = []
+    for p in net.parameters():      # (the engine calls a leaf's hook with None for a gradient the node added in place)
+        p.register_hook(lambda g_: fired.append(1) if g_ is not None else None)
+    before = {k: v.clone() for k, v in net.state_dict().items()}
+    tv, tn, tc = torch.from_numpy(voxels).to(dev), torch.from_numpy(nump).to(dev), torch.from_numpy(coors).to(dev)
+    gout = torch.from_numpy(rng.normal(size=(P, filters[-1])).astype(np.float32)).to(dev)
+    if inplace:
+        flat.grad.zero_()
+    out = net(tv, tn, tc)
+    fused = len(filters) == 1
+    assert (type(out.grad_fn.next_functions[0][0]).__name__ == "_PFNFusedBackward" or type(out.grad_fn).__name__ == "_PFNFusedBackward") == fused
+    out.backward(gout)
+    torch.cuda.synchronize()
+    if fused:
+        # the fused single layer takes its in-place targets in eval too (papc_pfn_bwd flags == 3) and hands autograd nothing; without
+        # FlatParams all three gradients come back through autograd
+        assert len(fired) == (0 if inplace else 3), "in-place targets %s: %d gradients went through autograd" % ("set" if inplace else "unset", len(fired))
+    else:
+        assert len(fired) == 6        # an eval-mode stack never takes in-place targets (mlp.shared_mlp_max)
+    x = torch.from_numpy(R.pillar_decorate(voxels, nump, coors, vs[0], vs[1], vs[0] / 2 + pr[0], vs[1] / 2 + pr[1])).to(dev).double()
+    p64 = []
+    for i, l in enumerate(net.pfn_layers):
+        t = [a.detach().double().requires_grad_(True) for a in (l.linear.weight, l.norm.weight, l.norm.bias)]
+        p64.append(t)
+        x = _torch_pfn_layer(x, t[0], t[1], t[2], None, i == len(filters) - 1, True, running=(l.norm.running_mean.double(), l.norm.running_var.double()))
+    tag = "PFN eval %s %s" % (filters, "in-place" if inplace else "fresh")
+    assert_close(_np(out), _np(x.squeeze()), REL, tag + ": out")
+    x.squeeze().backward(gout.double())
+    for i, l in enumerate(net.pfn_layers):
+        for nm, p, r in (("dW", l.linear.weight, p64[i][0]), ("dgamma", l.norm.weight, p64[i][1]), ("dbeta", l.norm.bias, p64[i][2])):
+            assert_close(_np(p.grad), _np(r.grad), GTOL, "%s: %s layer %d" % (tag, nm, i))
+    for k, v in net.state_dict().items():
+        assert torch.equal(v, before[k]), k
+    if inplace:
+        first = [p.grad.clone() for p in net.parameters()]
+        net(tv, tn, tc).backward(gout)
+        torch.cuda.synchronize()
+        for p, g1 in zip(net.parameters(), first):
+            assert torch.equal(p.grad, 2.0 * g1), "two backward passes are not twice the first"
+
+
+@pytest.mark.parametrize("fused_tails", [False, True])
+def test_pfn_raw_eval_backward_honours_both_flag_bits(dev, fused_tails):
+    """papc_pfn_bwd with training = 0 through raw ctypes, where the buffers' contents are the test's own: accumulate = 0 must OVERWRITE
+    (NaN-filled buffers come back finite and right), accumulate = 1 must ADD (prefill + fresh).  The finalize takes flags & 1 = eval and
+    flags & 2 = accumulate -- the opposite bit order to papc_bn_bwd_finalize_f32 -- in both its forms (the separate launch and the fold's tail)."""
+    import ctypes
+    from papc_amd.pillars import PfnDesc, PfnIo
+    lib = _lib.load()
+    P, T, Cc = 120, 30, 64
+    voxels, nump, coors = make_pillars(P, T, seed=4)
+    rng = np.random.default_rng(23)
+    w = (rng.normal(size=(Cc, 9)) * 0.3).astype(np.float32)
+    g = rng.uniform(0.5, 1.5, Cc).astype(np.float32) * rng.choice([1.0, -1.0], Cc).astype(np.float32)
+    b = (rng.normal(size=Cc) * 0.2).astype(np.float32)
+    rm, rv = _running(Cc, rng)
+    vs, pr = (0.16, 0.16, 4.0), (0.0, -39.68, -3.0, 69.12, 39.68, 1.0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+    feat, nv, co, wt, gt, bt, rmt, rvt = (t(a) for a in (voxels, nump, coors, w, g, b, rm, rv))
+    d = PfnDesc(P, T, Cc, vs[0], vs[1], vs[0] / 2 + pr[0], vs[1] / 2 + pr[1], 1e-3, 0.01, 0)
+    sb, wb = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(lib.papc_pfn_workspace(ctypes.byref(d), ctypes.byref(sb), ctypes.byref(wb)), "papc_pfn_workspace")
+    saved = torch.empty(sb.value, device=dev, dtype=torch.uint8)
+    scr = torch.empty(wb.value, device=dev, dtype=torch.uint8)
+    out = torch.empty(P, Cc, device=dev)
+    tickets = torch.zeros(2, device=dev, dtype=torch.int32)
+    io = PfnIo(feat.data_ptr(), nv.data_ptr(), co.data_ptr(), wt.data_ptr(), gt.data_ptr(), bt.data_ptr(), rmt.data_ptr(), rvt.data_ptr(), out.data_ptr(),
+               saved.data_ptr(), scr.data_ptr(), tickets.data_ptr() if fused_tails else None)
+    st = torch.cuda.current_stream().cuda_stream
+    _lib.check(lib.papc_pfn_fwd(ctypes.byref(d), ctypes.byref(io), st), "papc_pfn_fwd")
+    assert torch.equal(rmt.cpu(), torch.from_numpy(rm)) and torch.equal(rvt.cpu(), torch.from_numpy(rv))
+    gout = t(rng.normal(size=(P, Cc)).astype(np.float32))
+    rows = torch.from_numpy(R.pillar_decorate(voxels, nump, coors, vs[0], vs[1], vs[0] / 2 + pr[0], vs[1] / 2 + pr[1])).to(dev).double().reshape(P * T, 9)
+    w64, g64, b64 = (x.double().requires_grad_(True) for x in (wt, gt, bt))
+    z = (rows @ w64.t() - rmt.double()) / torch.sqrt(rvt.double() + 1e-3) * g64 + b64
+    o64 = torch.relu(z).reshape(P, T, Cc).max(1).values
+    tag = "papc_pfn_bwd eval (%s)" % ("fold tail" if fused_tails else "separate finalize")
+    assert_close(_np(out), _np(o64), REL, tag + ": out")
+    o64.backward(gout.double())
+    nan = float("nan")
+    fresh = [torch.full(s_, nan, device=dev) for s_ in ((Cc, 9), (Cc,), (Cc,))]
+    _lib.check(lib.papc_pfn_bwd(ctypes.byref(d), ctypes.byref(io), gout.data_ptr(), *(x.data_ptr() for x in fresh), 0, st), "papc_pfn_bwd")
+    acc = [torch.full(s_, 3.0 + i, device=dev) for i, s_ in enumerate(((Cc, 9), (Cc,), (Cc,)))]
+    _lib.check(lib.papc_pfn_bwd(ctypes.byref(d), ctypes.byref(io), gout.data_ptr(), *(x.data_ptr() for x in acc), 1, st), "papc_pfn_bwd")
+    torch.cuda.synchronize()
+    for i, (nm, got, a, want) in enumerate(zip(("dW", "dgamma", "dbeta"), fresh, acc, (w64.grad, g64.grad, b64.grad))):
+        assert bool(torch.isfinite(got).all()), "%s: accumulate = 0 added to what the buffer held (%s)" % (tag, nm)
+        assert_close(_np(got), _np(want), GTOL, "%s: %s" % (tag, nm))
+        # prefill + fresh: one fp32 add per element, 1.2e-7 of the larger operand (as the stack's accumulate case in tests/test_gpu_cabi.py)
+        err = float((a.double() - (3.0 + i + got.double())).abs().max())
+        scale = max(3.0 + i, float(got.abs().max()))
+        print("[accumulate] %s %s: |acc - (prefill + fresh)| = %.2e of %.2e (bar 1e-6)" % (tag, nm, err / scale, scale))
+        assert err <= 1e-6 * scale, "%s: accumulate = 1 is not prefill + fresh (%s)" % (tag, nm)
+    assert int(tickets.abs().sum()) == 0
+
+
+# ---- voxnet.voxconv_backbone --------------------------------------------------------------------------------------------------------------
+
+def test_voxconv_backbone_eval_with_grad_takes_the_torch_op_path(dev, monkeypatch):
+    """an eval-mode forward that records gradients runs the source's op sequence in torch device ops (the kernels' backward is the train-mode
+    norm's): the node is not _VoxBackbone, and logits and every parameter gradient agree with the float64 closed form on the running statistics"""
+    from papc_amd import voxnet
+    monkeypatch.setattr(voxnet, "_VOXNET", True)
+    B, E, NCLS = 3, 12, 10
+    assert voxnet.kernel_ok(E)
+    P64 = {k: v.float().double() for k, v in voxnet_ref.params(E, 31, NCLS).items()}
+    conv1, bn, conv2 = torch.nn.Conv3d(1, 32, 5, 2).to(dev), torch.nn.BatchNorm3d(32, eps=voxnet_ref.EPS).to(dev), torch.nn.Conv3d(32, 32, 3, 1).to(dev)
+    rng = np.random.default_rng(8)
+    rm, rv = _running(32, rng)
+    with torch.no_grad():
+        for mod, i in ((conv1, 0), (bn, 1), (conv2, 3)):
+            mod.weight.copy_(P64["backbone.%d.weight" % i].float())
+            mod.bias.copy_(P64["backbone.%d.bias" % i].float())
+        bn.running_mean.copy_(torch.from_numpy(rm))
+        bn.running_var.copy_(torch.from_numpy(rv))
+    head = {k: v.float().to(dev).requires_grad_(True) for k, v in P64.items() if k.startswith("head.")}
+    before = {k: v.clone() for k, v in bn.state_dict().items()}
+    x = torch.from_numpy((rng.uniform(size=(B, 1, E, E, E)) < 0.15).astype(np.float32)).to(dev)
+    with torch.no_grad():
+        flat_k = voxnet.voxconv_backbone(x, conv1, bn, conv2, False)          # no gradient recorded: the kernels
+    flat = voxnet.voxconv_backbone(x, conv1, bn, conv2, False)
+    assert flat.requires_grad and type(flat.grad_fn).__name__ != "_VoxBackboneBackward", type(flat.grad_fn).__name__
+    h = torch.nn.functional.leaky_relu(flat @ head["head.0.weight"].t() + head["head.0.bias"], voxnet_ref.SLOPE)
+    logits = h @ head["head.3.weight"].t() + head["head.3.bias"]
+    P = {k: v.clone().requires_grad_(True) for k, v in P64.items()}
+    ref, bb = voxnet_ref.closed(P, x.double().cpu(), stats=(torch.from_numpy(rm).double(), torch.from_numpy(rv).double()))
+    assert_close(_np(flat_k), _np(bb["flat"]), KD_BAR, "voxconv eval: kernels' flat (no grad)")
+    assert_close(_np(logits), _np(ref), KD_BAR, "voxconv eval: logits")
+    gout = torch.from_numpy(rng.normal(size=(B, NCLS)).astype(np.float32))
+    logits.backward(gout.to(dev))
+    ref.backward(gout.double())
+    got = {"backbone.0.weight": conv1.weight, "backbone.0.bias": conv1.bias, "backbone.1.weight": bn.weight, "backbone.1.bias": bn.bias,
+           "backbone.3.weight": conv2.weight, "backbone.3.bias": conv2.bias}
+    got.update(head)
+    for k, p in got.items():
+        assert_close(_np(p.grad), _np(P[k].grad), KD_BAR, "voxconv eval: d " + k)
+    for k, v in bn.state_dict().items():
+        assert torch.equal(v, before[k]), k
+
+
+# ---- whole models -------------------------------------------------------------------------------------------------------------------------
+# .eval() with grad enabled, one backward of (logits * G).sum(); every comparison at the model file's own bar.  Float32-vs-float64 drift of
+# each twin's stack decisions on the CPU (model_f32_drift): 0 in every stack -- pointnet_clas 0 of 204800 / 131072 / 204800 / 204800,
+#   pointnet_basic_clas 0 of 335872, pointnet_seg the same four and 0 of 524288 / 524288 (seg_net), pointnet_basic_seg 0 of 131072 / 198656 /
+#   524288 / 524288, kdunet 0 of 1703936 (all levels and up stacks together)
+MODEL_BAR = 2e-4     # BAR of tests/test_gpu_pointnet.py, test_gpu_pointnet_seg.py, test_gpu_kdunet.py
+MODEL_SEEDS = {"pointnet_clas": 37, "pointnet_basic_clas": 38, "pointnet_seg": 37, "pointnet_basic_seg": 37, "kdunet": 31}
+PN_B, PN_N = 4, 256
+
+
+def _seed_running(m, seed):
+    rng = np.random.default_rng(seed)
+    with torch.no_grad():
+        for mod in m.modules():
+            if isinstance(mod, torch.nn.modules.batchnorm._BatchNorm):
+                rm, rv = _running(mod.num_features, rng)
+                mod.running_mean.copy_(torch.from_numpy(rm))
+                mod.running_var.copy_(torch.from_numpy(rv))
+
+
+def _pn_model(kind, dev):
+    from papc_amd.models import PointNet_Basic_Clas
+    from tests import test_gpu_pointnet as TP
+    from tests import test_gpu_pointnet_seg as TS
+    from tests.util import copy_into_model, seeded_model_state
+    seed = MODEL_SEEDS[kind]
+    if kind == "pointnet_clas":
+        m = TP._seeded_model(dev, seed, N=PN_N)
+    elif kind == "pointnet_basic_clas":
+        m = PointNet_Basic_Clas(16).to(dev)
+        st = seeded_model_state(m, seed)
+        rng = np.random.default_rng(seed + 1)
+        for i, bn in enumerate(m.bns):       # (seeded_model_state knows a norm by "bn" / "norm" in its name: "bns.i" qualifies; negative gammas as elsewhere)
+            c = bn.num_features
+            st["bns.%d.weight" % i] = (rng.uniform(0.5, 1.5, size=c) * rng.choice([1.0, 1.0, 1.0, -1.0], size=c)).astype(np.float32)
+            st["bns.%d.bias" % i] = (rng.normal(size=c) * 0.2).astype(np.float32)
+        copy_into_model(m, st)
+    else:
+        m = TS._seeded_model(dev, "pointnet" if kind == "pointnet_seg" else "pointnet_basic", seed, N=PN_N)
+    _seed_running(m, seed + 2)
+    return m.eval()
+
+
+PN_STACKS = {"pointnet_clas": ["input_transform_net", "mlp_1", "feature_transform_net", "mlp_2"], "pointnet_basic_clas": ["stack"],
+             "pointnet_seg": ["input_transform_net", "mlp_1", "feature_transform_net", "mlp_2", "seg0", "seg1"],
+             "pointnet_basic_seg": ["mlp_1", "mlp_2", "seg0", "seg1"]}
+
+
+def _pn_twin(kind, P, x, dec, tally):
+    if kind == "pointnet_clas":
+        return pointnet_ref.pointnet_clas(P, x, train=False, dec=dec, tally=tally)
+    if kind == "pointnet_seg":
+        return pointnet_seg_ref.pointnet_seg(P, x, train=False, dec=dec, tally=tally)
+    if kind == "pointnet_basic_seg":
+        return pointnet_seg_ref.pointnet_basic_seg(P, x, train=False, dec=dec, tally=tally)
+    # PointNet_Basic_Clas (pointnet_base.py:7-45): one five-layer stack pooled over each cloud, then the FC head
+    B, _, N = x.shape
+    params = [(P["convs.%d.weight" % i].squeeze(-1), P["convs.%d.bias" % i], P["bns.%d.weight" % i], P["bns.%d.bias" % i]) for i in range(5)]
+    running = [(P["bns.%d.running_mean" % i], P["bns.%d.running_var" % i]) for i in range(5)]
+    rows = x.transpose(1, 2).reshape(B * N, 3)
+    d = dec.get("stack")
+    if isinstance(d, str):
+        d = torch_ref.own_decisions(rows.detach(), [tuple(a.detach() for a in q) for q in params], N, EPS, running)
+        tally.setdefault("own", []).append(d)
+    f, stats = torch_ref.stack_routed(rows, params, N, EPS, *d, running=running)
+    tally.setdefault("stacks", []).append(("stack", list(range(5)), stats))
+    return pointnet_ref.fc_block(P, "fc", f, [0, 2, 5], dec.get("fc"), tally=tally)
+
+
+def _pn_input(kind):
+    rng = np.random.default_rng(MODEL_SEEDS[kind] + 3)
+    nc = 16 if kind.endswith("clas") else 50
+    x = rng.normal(size=(PN_B, 3, PN_N)).astype(np.float32)
+    G = rng.normal(size=(PN_B, nc) if kind.endswith("clas") else (PN_B, PN_N, nc)).astype(np.float32)
+    return x, G
+
+
+def model_f32_drift(kind):
+    """CPU only: per stack of the twin, the decisions of a float32 run pinned into the float64 run -> [(stack, differing, of)]"""
+    if kind == "kdunet":
+        from papc_amd.models import KDUNet
+        from tests import test_gpu_kdunet as TK
+        from tests.util import copy_into_model, seeded_model_state
+        m = KDUNet(num_classes=TK.NC)
+        copy_into_model(m, seeded_model_state(m, MODEL_SEEDS[kind]))
+        _seed_running(m, MODEL_SEEDS[kind] + 2)
+        x, sels, _ = TK._inputs(2, 3)
+        run = lambda dt: {k: v.detach().to(dt) for k, v in m.named_buffers() if "running" in k}      # noqa: E731
+        exp = []
+        kdunet_ref.kdunet({k: v.detach().float() for k, v in m.named_parameters()}, torch.from_numpy(x), sels[:5], running=run(torch.float32), export=exp)
+        dec, up_dec = exp[:5], _kd_up_dec(exp[5:])
+        tally = {}
+        kdunet_ref.kdunet({k: v.detach().double() for k, v in m.named_parameters()}, torch.from_numpy(x).double(), sels[:5], dec=dec, up_dec=up_dec,
+                          running=run(torch.float64), tally=tally)
+        return [("kdunet", tally["winner_moves"] + tally["alive_flips"] + tally["relu_flips"], tally["decisions"])]
+    m = _pn_model(kind, torch.device("cpu"))
+    x, _ = _pn_input(kind)
+    own = {nm: "own" for nm in PN_STACKS[kind]}
+    t32 = {}
+    _pn_twin(kind, {k: v.detach().float() for k, v in m.state_dict().items()}, torch.from_numpy(x), own, t32)
+    t64 = {}
+    _pn_twin(kind, {k: v.detach().double() for k, v in m.state_dict().items()}, torch.from_numpy(x).double(), dict(zip(PN_STACKS[kind], t32["own"])), t64)
+    return [(nm, s["relu_flips"] + s["winner_moves"] + s["alive_flips"], s["decisions"]) for nm, _, s in t64["stacks"]]
+
+
+def _kd_up_dec(masks):
+    """the up half's ReLU masks in call order -> {(stack 1..5, layer 0..1): mask}: two layers per stack, the fifth has one"""
+    keys = [(i + 1, j) for i in range(5) for j in range(2 if i < 4 else 1)]
+    assert len(masks) == len(keys)
+    return dict(zip(keys, masks))
+
+
+@pytest.mark.parametrize("kind", ["pointnet_clas", "pointnet_basic_clas", "pointnet_seg", "pointnet_basic_seg"])
+def test_pointnet_models_eval_backward_vs_f64(dev, monkeypatch, kind):
+    import papc_amd.models as MD
+    import papc_amd.segment as S
+    import papc_amd.transform as T
+    m = _pn_model(kind, dev)
+    rec = {"stacks": [], "tnet": [], "concat": []}
+
+    def wrap(fn, key):
+        def inner(*a, **k):
+            out = fn(*a, **k)
+            rec[key].append(out)
+            return out
+        return inner
+    monkeypatch.setattr(MD, "shared_mlp_max", wrap(MD.shared_mlp_max, "stacks"))
+    monkeypatch.setattr(T, "tnet_fc", wrap(T.tnet_fc, "tnet"))
+    monkeypatch.setattr(S, "cloud_concat_bn_relu", wrap(S.cloud_concat_bn_relu, "concat"))
+    xh, Gh = _pn_input(kind)
+    x = torch.from_numpy(xh).to(dev)
+    wants_x = kind == "pointnet_basic_seg"          # the only one of the four whose every use of the input is differentiable (point rows)
+    if wants_x:
+        x.requires_grad_(True)
+    before = {k: v.clone() for k, v in m.state_dict().items()}
+    logits = m(x)
+    names = [n for n in PN_STACKS[kind] if n != "seg0"]
+    assert len(rec["stacks"]) == len(names), (len(rec["stacks"]), names)
+    dec = {}
+    for nm, out in zip(names, rec["stacks"]):
+        assert out.grad_fn.spec.eval_bn
+        argmax, alive, masks = kernel_decisions(out)
+        dec[nm] = (argmax.cpu() if argmax is not None else None, alive.cpu(), [None if mk is None else mk.cpu() for mk in masks])
+    for nm, out in zip(["input_fc", "feature_fc"], rec["tnet"]):
+        saved = out.grad_fn.saved_tensors             # _HeadPlain: (x0, w1, w2, w3, relu1 out, relu2 out)
+        dec[nm] = ((saved[4] > 0).cpu(), (saved[5] > 0).cpu(), None)
+    if kind.endswith("seg"):
+        assert len(rec["concat"]) == 1
+        dec["seg0"] = (None, (rec["concat"][0].detach() > 0).cpu(), None)
+    else:
+        saved = logits.grad_fn.saved_tensors
+        dec["fc"] = ((saved[4] > 0).cpu(), (saved[5] > 0).cpu(), None)      # eval: no dropout mask
+    P = {k: v.detach().double().cpu() for k, v in m.state_dict().items()}
+    for k, _ in m.named_parameters():
+        P[k].requires_grad_(True)
+    x64 = x.detach().double().cpu().requires_grad_(wants_x)
+    tally = {}
+    ref = _pn_twin(kind, P, x64, dec, tally)
+    assert [s[0].split(".")[-1] for s in tally["stacks"]] == [n if n not in ("seg0", "seg1") else "seg_net" for n in PN_STACKS[kind]]
+    for nm, (_, _, stats) in zip(PN_STACKS[kind], tally["stacks"]):
+        _cap(stats, "%s eval %s" % (kind, nm))
+    fcs = [k for k in ("input_fc", "feature_fc", "fc") if k in dec]
+    assert [f[0] for f in tally.get("fc", [])] == fcs
+    for nm, flips, of in tally.get("fc", []):      # the FC blocks' two hidden ReLUs are pinned as well: the same cap
+        _cap({"relu_flips": flips, "winner_moves": 0, "alive_flips": 0, "decisions": of}, "%s eval %s" % (kind, nm))
+    assert_close(_np(logits), _np(ref), MODEL_BAR, "%s eval logits" % kind)
+    logits.backward(torch.from_numpy(Gh).to(dev))
+    ref.backward(torch.from_numpy(Gh).double())
+    bad = []
+    for k, p in m.named_parameters():
+        assert p.grad is not None, k
+        try:
+            assert_close(_np(p.grad), _np(P[k].grad), MODEL_BAR, "%s eval d %s" % (kind, k))
+        except AssertionError as e:
+            bad.append(str(e))
+    if wants_x:
+        try:
+            assert_close(_np(x.grad), _np(x64.grad), MODEL_BAR, "%s eval d input" % kind)
+        except AssertionError as e:
+            bad.append(str(e))
+    assert not bad, bad
+    for k, v in m.state_dict().items():
+        assert torch.equal(v, before[k]), k
+
+
+def test_kdunet_eval_backward_vs_f64(dev, monkeypatch):
+    from papc_amd import kdnet
+    from tests import test_gpu_kdunet as TK
+    monkeypatch.setattr(kdnet, "_KDCONV", True)
+    B = 2
+    m = TK._seeded_model(dev, MODEL_SEEDS["kdunet"])
+    _seed_running(m, MODEL_SEEDS["kdunet"] + 2)
+    m.eval()
+    xh, sels, _ = TK._inputs(B, 3)
+    down, up = TK._recording(monkeypatch)
+    x = torch.from_numpy(xh).to(dev).requires_grad_(True)
+    split = torch.from_numpy(np.concatenate(sels, axis=1).astype(np.int32)).to(dev)
+    before = {k: v.clone() for k, v in m.state_dict().items()}
+    logits = m([x, split])
+    assert logits.shape == (B, 1024, TK.NC) and len(down) == 5 and len(up) == 5
+    dec, up_dec = [], {}
+    for out in down:
+        assert type(out.grad_fn).__name__ == "_KDConvBNBackward"
+        dec.append((out.grad_fn.saved_tensors[5].cpu(), (out.detach() > 0).cpu()))
+    for i, (L, out) in enumerate(up):
+        assert out.grad_fn.spec.eval_bn
+        _, alive, masks = kernel_decisions(out)
+        up_dec[(i + 1, L - 1)] = alive.cpu()
+        if L == 2:
+            assert masks[0] is not None       # in eval every layer's output is stored: every mask is pinned
+            up_dec[(i + 1, 0)] = masks[0].cpu()
+    P = {k: v.detach().double().cpu().requires_grad_(True) for k, v in m.named_parameters()}
+    running = {k: v.detach().double().cpu() for k, v in m.named_buffers() if "running" in k}
+    x64 = torch.from_numpy(xh).double().requires_grad_(True)
+    tally = {}
+    ref, _ = kdunet_ref.kdunet(P, x64, sels[:5], dec=dec, up_dec=up_dec, running=running, tally=tally)
+    _cap({k: tally.get(k, 0) for k in ("relu_flips", "winner_moves", "alive_flips", "decisions")}, "kdunet eval")
+    assert_close(_np(logits), _np(ref), MODEL_BAR, "kdunet eval logits")
+    G = torch.from_numpy(np.random.default_rng(7).normal(size=(B, 1024, TK.NC)).astype(np.float32))
+    logits.backward(G.to(dev))
+    ref.backward(G.double())
+    bad = []
+    for k, p in m.named_parameters():
+        assert p.grad is not None, k
+        try:
+            assert_close(_np(p.grad), _np(P[k].grad), MODEL_BAR, "kdunet eval d " + k)
+        except AssertionError as e:
+            bad.append(str(e))
+    try:
+        assert_close(_np(x.grad), _np(x64.grad), MODEL_BAR, "kdunet eval d input")
+    except AssertionError as e:
+        bad.append(str(e))
+    assert not bad, bad
+    for k, v in m.state_dict().items():
+        assert torch.equal(v, before[k]), k
