@@ -712,6 +712,32 @@ int papc_cloud_concat_conv_bwd_f32(const float *dz, const float *y, const float 
                                    int Cg, int Cout, float *dx, int64_t ldd, int accumulate, float *dw, float *dbias, float *dg, float *s_out,
                                    void *workspace, size_t workspace_bytes, papc_stream_t stream);
 
+/* The wide concat convs of the VFE models (classify/vfe/vfe.py:79-83: vfe.pointnet_2.mlp_1.0; segment/vfe/vfe.py:33-36: seg_net[0]),
+ * csrc/cloud_concat_k.hip: the same 1x1 conv over concat([x (Cp ch), tile(g (Cg ch), N)]) without forming the tile, K-looped over Cp.  Argument
+ * meaning, layouts and the rules for NULL arguments are those of papc_cloud_concat_conv_* above (w [Cout, Cp + Cg] read in place; stats_partial
+ * [papc_cloud_concat_k_parts(B, N), 2, Cout], NULL in eval mode; dY formed on the fly from dz, y and the BN constants; accumulate adds into dx;
+ * s_out optional).
+ *   papc_cloud_concat_k_ok       != 0 where the kernels take the widths
+ *   papc_cloud_concat_k_f32      c, then tiles of 128 rows x 128 columns of y (x 64 where Cout is no multiple of 128), a K loop over Cp in stages of 32
+ *   papc_cloud_concat_k_bwd_f32  dX_p through papc_mlp_bwd_dx_f32 (against W_p^T, written into the workspace) and dW_p through papc_mlp_bwd_dw_f32
+ *                                over at most 64 row ranges, folded into w's layout; the per-cloud column sums s of dY in 128-row segments, folded in
+ *                                order; dW_g, dbias, dg from s.  No atomics: bit-reproducible.  workspace: papc_cloud_concat_k_bwd_workspace(...)
+ *                                bytes = W_p^T, the dW_p range partials [ranges, Cout * Cp + Cout] (ranges = ceil(M / rows), rows = max(256, ceil(M / 64)
+ *                                rounded up to 64)), the column-sum partials [B * ceil(N / 128), Cout], s [B, Cout] and a dense dX [M, Cp] (used when
+ *                                accumulate != 0 or ldd != Cp); 0 for a shape the kernels refuse.
+ * Shapes: multiples of 64 with Cp in 64..256, Cg in 64..2304, Cout in 64..512 (else PAPC_E_UNSUPPORTED, naming the values); B <= 65535,
+ * B*N <= 2^30; x / w / dz / y, the BN constants and the workspace 16-byte aligned, ldx a multiple of 4.  The per-point products run on
+ * v_mfma_f32_32x32x16_bf16 through csrc/bf16x3.h (fp32 accuracy, fp32 accumulation), the per-cloud ones are fmaf chains in ascending order. */
+int papc_cloud_concat_k_ok(int Cp, int Cg, int Cout);
+int papc_cloud_concat_k_parts(int B, int N);
+int papc_cloud_concat_k_f32(const float *x, int64_t ldx, const float *g, const float *w, const float *bias, int B, int N, int Cp, int Cg, int Cout,
+                            float *y, float *cvec, float *stats_partial, papc_stream_t stream);
+size_t papc_cloud_concat_k_bwd_workspace(int B, int N, int Cp, int Cg, int Cout);
+int papc_cloud_concat_k_bwd_f32(const float *dz, const float *y, const float *mean, const float *invstd, const float *scale, const float *shift,
+                                const float *c1, const float *c2, const float *x, int64_t ldx, const float *g, const float *w, int B, int N, int Cp,
+                                int Cg, int Cout, float *dx, int64_t ldd, int accumulate, float *dw, float *dbias, float *dg, float *s_out,
+                                void *workspace, size_t workspace_bytes, papc_stream_t stream);
+
 /* One level of the KD-Net classifier (PAPC/models/classify/kdnet/kdnet.py:21-30): Conv1D(Cin, 3F, 1), ReLU, the kd-tree select, the max over
  * adjacent point pairs -- computing only the selected third of the conv (csrc/kdconv.hip).  Point-major rows: x [B * dim, Cin] at x + m*ldx,
  * out [B * dim / 2, F] contiguous, w [3F, Cin] (the Conv1D weight in place), bias [3F] (may be NULL), sel int32 split dims in 0..2 (values

@@ -155,6 +155,12 @@ SIGNATURES = {
     "papc_cloud_concat_conv_bwd_workspace": (ctypes.c_size_t, [c_i, c_i, c_i, c_i, c_i]),
     "papc_cloud_concat_conv_bwd_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_l, c_i, c_p, c_p,
                                              c_p, c_p, c_p, ctypes.c_size_t, c_p]),
+    "papc_cloud_concat_k_ok": (c_i, [c_i, c_i, c_i]),
+    "papc_cloud_concat_k_parts": (c_i, [c_i, c_i]),
+    "papc_cloud_concat_k_f32": (c_i, [c_p, c_l, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "papc_cloud_concat_k_bwd_workspace": (ctypes.c_size_t, [c_i, c_i, c_i, c_i, c_i]),
+    "papc_cloud_concat_k_bwd_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_l, c_i, c_p, c_p,
+                                          c_p, c_p, c_p, ctypes.c_size_t, c_p]),
     "papc_kdconv_ok": (c_i, [c_i, c_i, c_i]),
     "papc_kdconv_fwd_f32": (c_i, [c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
     "papc_kdconv_bwd_workspace": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),

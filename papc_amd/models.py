@@ -9,6 +9,7 @@
   KDNet                                    <- PAPC/models/classify/kdnet/kdnet.py:5-49
   KDUNet                                   <- PAPC/models/segment/kdunet/kdunet.py:5-115
   VoxNet                                   <- PAPC/models/classify/voxnet/voxnet.py:4-26
+  VFE_Clas / VFE_Seg                       <- PAPC/models/classify/vfe/vfe.py:5-86, PAPC/models/segment/vfe/vfe.py:5-97
 
 Inputs are ``[B,3,N]`` float32 (``[B,6,N]`` with normals).  Everything runs in libpapc_hip.so, in train AND eval mode, the FC heads included
 (head.py); the nn.Linear / BatchNorm1d / Dropout modules are the parameter holders.  CPU tensors raise PapcError (there is no CPU path); the
@@ -696,6 +697,118 @@ class KDUNet(nn.Module):
                 rows = self._cbr([pair[0]], B, n, rows)
                 rows = linear_rows(rows, pair[1].weight, pair[1].bias)
         return rows.view(B, N, -1)                                                               # :16 the final transpose: [B, N, classes]
+
+
+class _VFEPointNet(nn.Module):
+    """PointNet_Basic of vfe.py (classify :42-64, segment :53-75): mlp_1 = ConvBNReLU x 2, mlp_2 = ConvBNReLU x 3 under the source's names"""
+
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.mlp_1 = nn.Sequential(_ConvBNReLU(cin, 64), _ConvBNReLU(64, 64))
+        self.mlp_2 = nn.Sequential(_ConvBNReLU(64, 64), _ConvBNReLU(64, 128), _ConvBNReLU(128, cout))
+
+    def blocks(self):
+        return list(self.mlp_1) + list(self.mlp_2)
+
+
+class _VFE(nn.Module):
+    """VFE of vfe.py (classify :66-86, segment :77-97): pointnet_1 per point, its max over the cloud tiled next to it, pointnet_2 pooled.
+    pointnet_1 is one shared-MLP stack without the max, the max is pillars._GroupMax (x1 is post-ReLU), pointnet_2.mlp_1.0 runs on
+    vfe.concat_k_bn_relu (the [B*N, 512] concat is never formed), the other four layers of pointnet_2 are one stack with the max."""
+
+    def __init__(self, feature_channels=256, max_points=1024):
+        super().__init__()
+        self.max_points = int(max_points)
+        self.pointnet_1 = _VFEPointNet(3, feature_channels)
+        self.pointnet_2 = _VFEPointNet(feature_channels * 2, max_points)
+
+    @staticmethod
+    def _cbr(blocks, B, N, x_rows, pool, training):
+        convs, bns = [m._conv for m in blocks], [m._batch_norm for m in blocks]
+        spec = StackSpec(B, N, 1, N, 0, xyz_first=True, eps=bns[0].eps, momentum=0.9, pool=pool, eval_bn=not training)
+        return shared_mlp_max(spec, _bn_buffers(bns), None, None, None, None, _stack_params(convs, bns), x_rows=x_rows)
+
+    def features(self, x, training):
+        """x [B, 3, N] -> (x1 [B*N, C], g1 = max_n x1 [B, C], x2 = max_n pointnet_2(concat) [B, max_points])"""
+        from .copyops import contiguous_copy
+        from .pillars import _GroupMax
+        from .vfe import concat_k_bn_relu
+        B, _, N = x.shape
+        pts = contiguous_copy(x.transpose(1, 2)).view(B * N, 3)                  # the planar coordinates as point rows
+        x1 = self._cbr(self.pointnet_1.blocks(), B, N, pts, False, training)     # x1 -> [B*N, C]
+        g1 = _GroupMax.apply(x1, B, N)                                           # paddle.max(x1, axis=-1) -> [B, C]
+        p2 = self.pointnet_2.blocks()
+        h = concat_k_bn_relu(x1, g1, p2[0]._conv, p2[0]._batch_norm, N, training)    # tile + concat + mlp_1.0 -> [B*N, 64]
+        x2 = self._cbr(p2[1:], B, N, h, True, training)                          # -> [B, max_points]
+        return x1, g1, x2
+
+
+class VFE_Clas(nn.Module):
+    """VFE classifier (PAPC/models/classify/vfe/vfe.py:5-86): the VFE features pooled over each cloud, then the FC head of PointNet_Basic_Clas.
+    Module names and shapes are the source's, so checkpoint.export_state / import_state exchange .pdparams with it directly.  The source tiles
+    by max_points: inputs must have N == max_points.  forward(inputs [B, 3, N]) -> [B, num_classes]"""
+
+    def __init__(self, num_classes=16, max_points=1024):
+        super().__init__()
+        self.max_points = int(max_points)
+        self.vfe = _VFE(max_points=max_points)                                                              # :8
+        self.fc = nn.Sequential(nn.Linear(max_points, 512), nn.ReLU(), nn.Linear(512, 256), nn.ReLU(), nn.Dropout(p=0.7),
+                                nn.Linear(256, num_classes))                                                # :9-16
+
+    def forward(self, inputs):
+        import numpy as np
+        dev = next(self.parameters()).device
+        if isinstance(inputs, np.ndarray) and dev.type == "cuda":                                           # :24 paddle.to_tensor of a loader batch
+            inputs = torch.from_numpy(np.ascontiguousarray(inputs, dtype=np.float32)).to(dev)
+        x = torch.as_tensor(inputs).float()
+        if not x.is_cuda or dev != x.device:
+            raise _lib.PapcError("VFE_Clas needs CUDA (ROCm) tensors and parameters on one device: there is no CPU fallback")
+        if x.dim() != 3 or x.shape[1] != 3:
+            raise _lib.PapcError("VFE_Clas: points [B, 3, %d] expected, got %s" % (self.max_points, tuple(x.shape)))
+        if x.shape[2] != self.max_points:
+            raise _lib.PapcError("VFE_Clas: the source tiles the cloud feature by max_points: N = %d points per cloud, max_points = %d"
+                                 % (x.shape[2], self.max_points))
+        _, _, feat = self.vfe.features(x, self.training)                                                    # :25, [B, max_points]
+        if _FUSED_HEAD and _head.plain_usable(feat, self.fc[0], self.fc[2], self.fc[5], self.training):
+            spec = self.__dict__.get("_head_spec")
+            if spec is None:
+                spec = self.__dict__["_head_spec"] = _head.HeadSpec()
+            return _head.plain_head(spec, feat, self.fc[0], self.fc[2], self.fc[4], self.fc[5], training=self.training)   # :26 on the head kernels
+        return self.fc(feat)                                                                                # :26
+
+
+class VFE_Seg(nn.Module):
+    """VFE part segmenter (PAPC/models/segment/vfe/vfe.py:5-97): seg_net over concat([x1, tile(max x1), tile(x2)]).  seg_net[0..2] runs on
+    vfe.concat_k_bn_relu with the per-cloud vector [max x1 | x2], [3..11] on one shared-MLP stack without the max, [12] on linear.linear_rows.
+    Module names and shapes are the source's.  Inputs must have N == max_points.  forward(inputs) takes the loader's [data, label] batch or a
+    bare [B, 3, N] tensor -> [B, N, num_classes]"""
+
+    _stack = PointNet_Clas._stack
+
+    def __init__(self, feature_channels=256, num_classes=50, max_points=1024):
+        super().__init__()
+        self.max_points = int(max_points)
+        self.vfe = _VFE(feature_channels, max_points)                                                       # :9
+        self.seg_net = _seg_net(max_points + feature_channels * 2, num_classes)                             # :10-24
+
+    def forward(self, inputs):
+        from .linear import linear_rows
+        from .vfe import concat_k_bn_relu
+        x = _seg_input(self, inputs)                                                                        # :32 inputs[0], [B, 3, N]
+        if next(self.parameters()).device != x.device:
+            raise _lib.PapcError("VFE_Seg needs CUDA (ROCm) tensors and parameters on one device: there is no CPU fallback")
+        if x.dim() != 3 or x.shape[1] != 3:
+            raise _lib.PapcError("VFE_Seg: points [B, 3, %d] expected, got %s" % (self.max_points, tuple(x.shape)))
+        B, _, N = x.shape
+        if N != self.max_points:
+            raise _lib.PapcError("VFE_Seg: the source tiles the cloud features by max_points: N = %d points per cloud, max_points = %d"
+                                 % (N, self.max_points))
+        x1, g1, x2 = self.vfe.features(x, self.training)                                                    # :33
+        s = self.seg_net
+        g = cat_copy([g1.unsqueeze(0), x2.unsqueeze(0)], 2).squeeze(0)                                      # the per-cloud half of :34-35, [B, C + P]
+        h = concat_k_bn_relu(x1, g, s[0], s[1], N, self.training)                                           # :36 seg_net[0..2] -> [B*N, 512]
+        h = self._stack(list(s)[3:12], B, N, False, x_rows=h)                                               # [B*N, 128]
+        return linear_rows(h, s[12].weight, s[12].bias).view(B, N, -1)                                      # :36-37
 
 
 class VoxNet(nn.Module):
