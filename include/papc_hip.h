@@ -702,7 +702,8 @@ int papc_cloud_transform_bwd_f32(const float *x, int64_t sb, int64_t sn, int64_t
  *                                dY in chunks of 128 rows of one cloud (dX rows and per-chunk partials), a fixed-order fold, the per-cloud tail.
  *                                No atomics: bit-reproducible.  workspace: papc_cloud_concat_conv_bwd_workspace(B, N, Cp, Cg, Cout) bytes.
  * Shapes: Cp = 64, Cg in 64..1024 (a multiple of 64), Cout = 512 (else PAPC_E_UNSUPPORTED); B <= 65535, B*N <= 2^30; x / w / dz / y and the
- * BN constants 16-byte aligned, ldx a multiple of 4.  Products on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation). */
+ * BN constants 16-byte aligned, ldx a multiple of 4.  Products on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation).
+ * What this family shares with papc_cloud_concat_k_* below (c, the forward epilogue, dY, the fold of s, the tail, the checks): csrc/cloud_concat.h. */
 int papc_cloud_concat_conv_parts(int B, int N);
 int papc_cloud_concat_conv_f32(const float *x, int64_t ldx, const float *g, const float *w, const float *bias, int B, int N, int Cp, int Cg, int Cout,
                                float *y, float *cvec, float *stats_partial, papc_stream_t stream);
@@ -727,7 +728,8 @@ int papc_cloud_concat_conv_bwd_f32(const float *dz, const float *y, const float 
  *                                accumulate != 0 or ldd != Cp); 0 for a shape the kernels refuse.
  * Shapes: multiples of 64 with Cp in 64..256, Cg in 64..2304, Cout in 64..512 (else PAPC_E_UNSUPPORTED, naming the values); B <= 65535,
  * B*N <= 2^30; x / w / dz / y, the BN constants and the workspace 16-byte aligned, ldx a multiple of 4.  The per-point products run on
- * v_mfma_f32_32x32x16_bf16 through csrc/bf16x3.h (fp32 accuracy, fp32 accumulation), the per-cloud ones are fmaf chains in ascending order. */
+ * v_mfma_f32_32x32x16_bf16 through csrc/bf16x3.h (fp32 accuracy, fp32 accumulation), the per-cloud ones are fmaf chains in ascending order
+ * (c and the tail are the kernels of papc_cloud_concat_conv_*: csrc/cloud_concat.h). */
 int papc_cloud_concat_k_ok(int Cp, int Cg, int Cout);
 int papc_cloud_concat_k_parts(int B, int N);
 int papc_cloud_concat_k_f32(const float *x, int64_t ldx, const float *g, const float *w, const float *bias, int B, int N, int Cp, int Cg, int Cout,

@@ -7,7 +7,10 @@ Public surface mirrors the reference:
   papc_amd.models      <- PointNet2_SSG_Clas / PointNet2_MSG_Clas / PointNet_Basic_Clas / PointNet_Clas (T-Net PointNet),
                           PointNet2_SSG_Seg / PointNet2_MSG_Seg / PointNet_Seg / PointNet_Basic_Seg, KDNet, KDUNet, VoxNet
   papc_amd.transform   <- the T-Net PointNet's per-cloud transform x . T[b] and its T-Net FC blocks
-  papc_amd.segment     <- the PointNet segmenters' first seg_net layer over concat([point, tile(global)]) without the tile
+  papc_amd.cloudconcat <- relu(bn(conv(concat([point, tile(global)])))) without the tile: the autograd node and BatchNorm sequence of both
+                          concat-conv kernel families
+  papc_amd.segment     <- the PointNet segmenters' first seg_net layer on it (the Cp = 64 family)
+  papc_amd.vfe         <- the VFE models' wide concat layers on it (the K-looped family)
   papc_amd.kdnet       <- one KD-Net level (conv, ReLU, kd-tree select, pair max) computing only the selected third of the conv, and the KDUNet
                           down level (the same behind a BatchNorm whose statistics come from the input rows' moments)
   papc_amd.voxnet      <- the VoxNet backbone (two 3-D convs as implicit GEMMs, the norm on load, the pool in registers), the head's LeakyReLU +

@@ -1,6 +1,6 @@
 // cloud_concat.hip -- the first seg_net layer of the PointNet part segmenters, for gfx950.
 //
-// Reference: /root/reference/PAPC/models/segment/pointnet/pointnet.py:105-107 and pointnet_base/pointnet_base.py:32-35:
+// Reference: PAPC/models/segment/pointnet/pointnet.py:105-107 and pointnet_base/pointnet_base.py:32-35:
 //     x = concat([point_feat (Cp ch), tile(global_feat (Cg ch), N)]);  y = Conv1D(Cp + Cg, Cout, 1)(x)
 // The tiled half is the same for every point of a cloud, so with W = [W_p | W_g] (W_p = W[:, :Cp]):
 //     y[b, n, :] = W_p . x[b, n, :] + c[b, :]          c[b, :] = W_g . g[b, :] + bias
@@ -14,25 +14,20 @@
 //             constants (as every backward kernel of the stack does), a chunk writes its dX rows, its partial dW_p and its partial column
 //             sums to slots of its own; cc_fold_kernel folds them in chunk order (fold.h); cc_tail_kernel forms dW_g, d bias and dg from s.
 //             No float atomics: two runs are bit-identical.
+// cloud_concat.h holds what this family shares with the K-looped one (cloud_concat_k.hip): the forward epilogue, dY, the fold of s, the
+// argument checks.  cc_cvec_kernel and cc_tail_kernel are defined here and serve both families through cc_launch_cvec / cc_launch_tail.
 // Products: v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation: the PAPC_GEMM_F32 arithmetic of papc_mlp_gemm_f32).  At
 // K = 64 the layer is bound by the [M, Cout] traffic of y and dY, not by the matrix rate.  The small per-cloud products are fmaf chains
 // in ascending index order.  Plain C++ loads and stores only.
-#include "fold.h"
+#include "cloud_concat.h"
 
 namespace papc {
 
-typedef float cc_floatx16 __attribute__((ext_vector_type(16)));
-
-constexpr int CC_T = 256;        // threads of every kernel here (4 waves)
-constexpr int CC_BM = 128;       // rows per tile (forward) / per chunk (backward)
 constexpr int CC_BN = 128;       // output columns per forward tile
 constexpr int CC_CP = 64;        // the point-feature width the kernels are written for
 constexpr int CC_OB = 64;        // output columns per backward column block
 constexpr int CC_LDA = 68;       // LDS pitch (floats) of the float4-read tiles
 constexpr int CC_LDX = 65;       // LDS pitch of the backward x tile (scalar reads)
-
-__device__ __forceinline__ float4 cc_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ void cc_st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
 
 // ---- forward ------------------------------------------------------------------------------------------------------------------------
 // c[b, o] = bias[o] + sum_k W[o, Cp + k] g[b, k]: workgroup (16 outputs, cloud b), wave = 4 outputs, lane = k (mod 64)
@@ -52,26 +47,27 @@ __global__ __launch_bounds__(CC_T) void cc_cvec_kernel(const float *__restrict__
     }
 }
 
-// y tile [128 rows, 128 columns] = x . W_p^T + c[b(row)]; 4 waves of 64 x 64 (2 x 2 MFMA blocks); K = 64 staged whole in LDS
+// y tile [128 rows, 128 columns] = x . W_p^T + c[b(row)]; 4 waves of 64 x 64 (2 x 2 MFMA blocks); K = 64 staged whole in LDS; the epilogue
+// (c[b(row)], the store, the tile's BatchNorm partials) is cloud_concat.h's
 __global__ __launch_bounds__(CC_T) void cc_fwd_kernel(const float *__restrict__ x, int64_t ldx, const float *__restrict__ w, int64_t ldw,
                                                       const float *__restrict__ cvec, int M, int N, int Cout, float *__restrict__ y,
                                                       float *__restrict__ stats)
 {
     __shared__ float xs[CC_BM * CC_LDA];
     __shared__ float ws[CC_BN * CC_LDA];
-    __shared__ float red[2][CC_BN];
+    __shared__ float red[2][2][CC_BN];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, hi = lane >> 5;
     const int n0 = blockIdx.x * CC_BN;
     const int m0 = blockIdx.y * CC_BM;
     for (int e = tid; e < CC_BM * 16; e += CC_T) {
         const int r = e >> 4, q = (e & 15) * 4;
         const int m = m0 + r;
-        cc_st4(&xs[r * CC_LDA + q], m < M ? cc_ld4(x + (int64_t)m * ldx + q) : make_float4(0.f, 0.f, 0.f, 0.f));
-        cc_st4(&ws[r * CC_LDA + q], cc_ld4(w + (int64_t)(n0 + r) * ldw + q));
+        st4(&xs[r * CC_LDA + q], m < M ? ld4(x + (int64_t)m * ldx + q) : make_float4(0.f, 0.f, 0.f, 0.f));
+        st4(&ws[r * CC_LDA + q], ld4(w + (int64_t)(n0 + r) * ldw + q));
     }
     __syncthreads();
     const int wm = wv & 1, wn = wv >> 1;
-    cc_floatx16 acc[2][2];
+    floatx16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -83,9 +79,9 @@ __global__ __launch_bounds__(CC_T) void cc_fwd_kernel(const float *__restrict__ 
     for (int kk = 0; kk < CC_CP; kk += 8) {
         float4 a[2], bq[2];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) a[i] = cc_ld4(&xs[(wm * 64 + i * 32 + l31) * CC_LDA + kk + 4 * hi]);
+        for (int i = 0; i < 2; ++i) a[i] = ld4(&xs[(wm * 64 + i * 32 + l31) * CC_LDA + kk + 4 * hi]);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) bq[j] = cc_ld4(&ws[(wn * 64 + j * 32 + l31) * CC_LDA + kk + 4 * hi]);
+        for (int j = 0; j < 2; ++j) bq[j] = ld4(&ws[(wn * 64 + j * 32 + l31) * CC_LDA + kk + 4 * hi]);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -96,48 +92,7 @@ __global__ __launch_bounds__(CC_T) void cc_fwd_kernel(const float *__restrict__ 
                 acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].w, bq[j].w, acc[i][j], 0, 0, 0);
             }
     }
-    // epilogue: C layout col = l31, row = (r & 3) + 8 (r >> 2) + 4 hi.  Rows past M are neither stored nor counted.
-    float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            if (m < M) {
-                const float *cb = cvec + (int64_t)(m / N) * Cout;
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int col = n0 + wn * 64 + j * 32 + l31;
-                    const float v = acc[i][j][r] + cb[col];
-                    y[(int64_t)m * Cout + col] = v;
-                    s1[j] += v;
-                    s2[j] = fmaf(v, v, s2[j]);
-                }
-            }
-        }
-    if (!stats) return;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {       // the two row halves of a lane pair, then the two row halves of the tile (wm), in fixed order
-        s1[j] += __shfl_xor(s1[j], 32);
-        s2[j] += __shfl_xor(s2[j], 32);
-    }
-    if (wm == 1 && hi == 0) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            red[0][wn * 64 + j * 32 + l31] = s1[j];
-            red[1][wn * 64 + j * 32 + l31] = s2[j];
-        }
-    }
-    __syncthreads();
-    if (wm == 0 && hi == 0) {
-        float *sp = stats + (int64_t)blockIdx.y * 2 * Cout;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int cl = wn * 64 + j * 32 + l31;
-            sp[n0 + cl] = s1[j] + red[0][cl];
-            sp[Cout + n0 + cl] = s2[j] + red[1][cl];
-        }
-    }
+    cc_fwd_epilogue<2, 2, CC_BN>(acc, red, cvec, wm, wn, blockIdx.y, m0, n0, M, N, Cout, y, stats);
 }
 
 // ---- backward -----------------------------------------------------------------------------------------------------------------------
@@ -161,10 +116,10 @@ __global__ __launch_bounds__(CC_T) void cc_bwd_kernel(const float *__restrict__ 
     const int64_t slot = (int64_t)b * nch + ch;
     for (int e = tid; e < CC_BM * 16; e += CC_T) {
         const int r = e >> 4, q = (e & 15) * 4;
-        const float4 v = r < rows ? cc_ld4(x + (mr0 + r) * ldx + q) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 v = r < rows ? ld4(x + (mr0 + r) * ldx + q) : make_float4(0.f, 0.f, 0.f, 0.f);
         xs[r * CC_LDX + q] = v.x; xs[r * CC_LDX + q + 1] = v.y; xs[r * CC_LDX + q + 2] = v.z; xs[r * CC_LDX + q + 3] = v.w;
     }
-    cc_floatx16 dxa[2];
+    floatx16 dxa[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -175,30 +130,24 @@ __global__ __launch_bounds__(CC_T) void cc_bwd_kernel(const float *__restrict__ 
             const int r = e >> 4, q = (e & 15) * 4, o = o0 + q;
             float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
             if (r < rows) {
-                const float4 zz = cc_ld4(dz + (mr0 + r) * Cout + o), yy = cc_ld4(yv + (mr0 + r) * Cout + o);
-                const float4 sc = cc_ld4(scale + o), sh = cc_ld4(shift + o), mu = cc_ld4(mean + o), is = cc_ld4(invstd + o);
-                const float4 k1 = cc_ld4(c1 + o), k2 = cc_ld4(c2 + o);
-                // dy = scale (p - c1 - xhat c2), p = dz where scale y + shift > 0 (mlp_loaders.h: dy_elem)
-                d.x = sc.x * ((((fmaf(sc.x, yy.x, sh.x) > 0.f) ? zz.x : 0.f) - k1.x) - (yy.x - mu.x) * is.x * k2.x);
-                d.y = sc.y * ((((fmaf(sc.y, yy.y, sh.y) > 0.f) ? zz.y : 0.f) - k1.y) - (yy.y - mu.y) * is.y * k2.y);
-                d.z = sc.z * ((((fmaf(sc.z, yy.z, sh.z) > 0.f) ? zz.z : 0.f) - k1.z) - (yy.z - mu.z) * is.z * k2.z);
-                d.w = sc.w * ((((fmaf(sc.w, yy.w, sh.w) > 0.f) ? zz.w : 0.f) - k1.w) - (yy.w - mu.w) * is.w * k2.w);
+                const float4 zz = ld4(dz + (mr0 + r) * Cout + o), yy = ld4(yv + (mr0 + r) * Cout + o);
+                cc_dy4(d, zz, yy, ld4(scale + o), ld4(shift + o), ld4(mean + o), ld4(invstd + o), ld4(c1 + o), ld4(c2 + o));
             }
-            cc_st4(&gs[r * CC_LDA + q], d);
+            st4(&gs[r * CC_LDA + q], d);
         }
         for (int e = tid; e < CC_OB * (CC_CP / 4); e += CC_T) {
             const int o = e >> 4, k = (e & 15) * 4;
-            const float4 v = cc_ld4(w + (int64_t)(o0 + o) * ldw + k);
+            const float4 v = ld4(w + (int64_t)(o0 + o) * ldw + k);
             wt[k * CC_LDA + o] = v.x; wt[(k + 1) * CC_LDA + o] = v.y; wt[(k + 2) * CC_LDA + o] = v.z; wt[(k + 3) * CC_LDA + o] = v.w;
         }
         __syncthreads();
         // dX[m][k] += sum_o dY[m][o] W[o][k]:  A[m][o] = gs, B[o][k] = wt[k][o]
 #pragma unroll
         for (int oo = 0; oo < CC_OB; oo += 8) {
-            const float4 a = cc_ld4(&gs[(wv * 32 + l31) * CC_LDA + oo + 4 * hi]);
+            const float4 a = ld4(&gs[(wv * 32 + l31) * CC_LDA + oo + 4 * hi]);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const float4 bq = cc_ld4(&wt[(j * 32 + l31) * CC_LDA + oo + 4 * hi]);
+                const float4 bq = ld4(&wt[(j * 32 + l31) * CC_LDA + oo + 4 * hi]);
                 dxa[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, bq.x, dxa[j], 0, 0, 0);
                 dxa[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, bq.y, dxa[j], 0, 0, 0);
                 dxa[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, bq.z, dxa[j], 0, 0, 0);
@@ -207,7 +156,7 @@ __global__ __launch_bounds__(CC_T) void cc_bwd_kernel(const float *__restrict__ 
         }
         // partial dW_p[o][k] = sum_r dY[r][o] X[r][k]:  A[o][r] = gs[r][o], B[r][k] = xs[r][k]; wave: o block (wv & 1), k block (wv >> 1)
         const int ob = (wv & 1) * 32, kb = (wv >> 1) * 32;
-        cc_floatx16 dwa;
+        floatx16 dwa;
 #pragma unroll
         for (int r = 0; r < 16; ++r) dwa[r] = 0.f;
 #pragma unroll 8
@@ -251,10 +200,7 @@ __global__ __launch_bounds__(CC_T) void cc_fold_kernel(const float *__restrict__
         dw[(t / CC_CP) * ldw + (t % CC_CP)] = fold_in_order<4, FOLD_FROM_ZERO, float>(part_w, nw, B * nch, t);
         return;
     }
-    const int64_t u = t - nw;
-    if (u >= (int64_t)B * Cout) return;
-    const int64_t b = u / Cout, o = u - b * Cout;
-    s[u] = fold_in_order<1, FOLD_FROM_ZERO, float>(part_s, Cout, nch, b * nch * Cout + o);
+    cc_fold_s(part_s, B, nch, Cout, t - nw, s);
 }
 
 // from s [B, Cout]: dW_g[o][k] = sum_b s[b][o] g[b][k] (into w's layout at column Cp + k), dg[b][k] = sum_o s[b][o] W[o][Cp + k],
@@ -286,12 +232,23 @@ __global__ __launch_bounds__(CC_T) void cc_tail_kernel(const float *__restrict__
     }
 }
 
+void cc_launch_cvec(hipStream_t st, const float *g, const float *w, int64_t ldw, const float *bias, int B, int Cp, int Cg, int Cout, float *cvec)
+{
+    hipLaunchKernelGGL(cc_cvec_kernel, dim3((unsigned)(Cout / 16), (unsigned)B), dim3(CC_T), 0, st, g, w, ldw, bias, Cp, Cg, Cout, cvec);
+}
+
+void cc_launch_tail(hipStream_t st, const float *s, const float *g, const float *w, int64_t ldw, int B, int Cp, int Cg, int Cout, float *dw, float *dbias,
+                    float *dg)
+{
+    const int64_t n_tail = (int64_t)Cout * Cg + (dg ? (int64_t)B * Cg : 0) + (dbias ? Cout : 0);
+    hipLaunchKernelGGL(cc_tail_kernel, dim3((unsigned)cdiv(n_tail, CC_T)), dim3(CC_T), 0, st, s, g, w, ldw, B, Cp, Cg, Cout, dw, dbias, dg);
+}
+
 static int cc_shape_ok(const char *who, int B, int N, int Cp, int Cg, int Cout)
 {
     PAPC_REQUIRE(Cp == CC_CP && Cg >= 64 && Cg <= 1024 && Cg % 64 == 0 && Cout == 512, PAPC_E_UNSUPPORTED,
                  "%s: Cp=%d Cg=%d Cout=%d (Cp = 64, Cg in 64..1024 and a multiple of 64, Cout = 512)", who, Cp, Cg, Cout);
-    PAPC_REQUIRE(B >= 1 && B <= 65535 && N >= 1 && (int64_t)B * N <= ((int64_t)1 << 30), PAPC_E_INVALID, "%s: B=%d N=%d", who, B, N);
-    return PAPC_OK;
+    return cc_range_ok(who, B, N);
 }
 
 static int64_t cc_chunks(int N) { return cdiv(N, CC_BM); }
@@ -302,25 +259,18 @@ using namespace papc;
 
 extern "C" {
 
-int papc_cloud_concat_conv_parts(int B, int N)
-{
-    if (B < 1 || N < 1) return 0;
-    return (int)cdiv((int64_t)B * N, CC_BM);
-}
+int papc_cloud_concat_conv_parts(int B, int N) { return cc_parts(B, N); }
 
 int papc_cloud_concat_conv_f32(const float *x, int64_t ldx, const float *g, const float *w, const float *bias, int B, int N, int Cp, int Cg, int Cout,
                                float *y, float *cvec, float *stats_partial, papc_stream_t stream)
 {
-    PAPC_REQUIRE(x && g && w && y && cvec, PAPC_E_INVALID, "papc_cloud_concat_conv_f32: null pointer");
-    const int err = cc_shape_ok("papc_cloud_concat_conv_f32", B, N, Cp, Cg, Cout);
+    const int err = cc_fwd_args_ok("papc_cloud_concat_conv_f32", cc_shape_ok, x, ldx, g, w, B, N, Cp, Cg, Cout, y, cvec);
     if (err != PAPC_OK) return err;
-    PAPC_REQUIRE(ldx >= Cp && ldx % 4 == 0 && aligned16(x) && aligned16(w), PAPC_E_INVALID,
-                 "papc_cloud_concat_conv_f32: x and w must be 16-byte aligned, ldx=%lld a multiple of 4 >= Cp", (long long)ldx);
     hipStream_t st = as_stream(stream);
     ProfScope prof(PAPC_K_MISC, st);
     const int64_t ldw = (int64_t)Cp + Cg;
     const int M = B * N;
-    hipLaunchKernelGGL(cc_cvec_kernel, dim3((unsigned)(Cout / 16), (unsigned)B), dim3(CC_T), 0, st, g, w, ldw, bias, Cp, Cg, Cout, cvec);
+    cc_launch_cvec(st, g, w, ldw, bias, B, Cp, Cg, Cout, cvec);
     const int e = check_launch("papc_cloud_concat_conv_f32: c");
     if (e != PAPC_OK) return e;
     hipLaunchKernelGGL(cc_fwd_kernel, dim3((unsigned)(Cout / CC_BN), (unsigned)cdiv(M, CC_BM)), dim3(CC_T), 0, st, x, ldx, w, ldw, cvec, M, N, Cout, y,
@@ -340,14 +290,9 @@ int papc_cloud_concat_conv_bwd_f32(const float *dz, const float *y, const float 
                                    int Cg, int Cout, float *dx, int64_t ldd, int accumulate, float *dw, float *dbias, float *dg, float *s_out,
                                    void *workspace, size_t workspace_bytes, papc_stream_t stream)
 {
-    PAPC_REQUIRE(dz && y && mean && invstd && scale && shift && c1 && c2 && x && g && w && dw && workspace, PAPC_E_INVALID,
-                 "papc_cloud_concat_conv_bwd_f32: null pointer");
-    const int err = cc_shape_ok("papc_cloud_concat_conv_bwd_f32", B, N, Cp, Cg, Cout);
+    const int err = cc_bwd_args_ok("papc_cloud_concat_conv_bwd_f32", cc_shape_ok, dz, y, mean, invstd, scale, shift, c1, c2, x, ldx, g, w, B, N, Cp, Cg,
+                                   Cout, dx, ldd, dw, workspace, true);
     if (err != PAPC_OK) return err;
-    PAPC_REQUIRE(ldx >= Cp && ldx % 4 == 0 && aligned16(x) && aligned16(w) && aligned16(dz) && aligned16(y) && aligned16(mean) && aligned16(invstd)
-                 && aligned16(scale) && aligned16(shift) && aligned16(c1) && aligned16(c2) && (!dx || ldd >= Cp), PAPC_E_INVALID,
-                 "papc_cloud_concat_conv_bwd_f32: operands must be 16-byte aligned, ldx=%lld a multiple of 4 >= Cp, ldd=%lld >= Cp",
-                 (long long)ldx, (long long)ldd);
     const size_t need = papc_cloud_concat_conv_bwd_workspace(B, N, Cp, Cg, Cout);
     PAPC_REQUIRE(workspace_bytes >= need, PAPC_E_INVALID, "papc_cloud_concat_conv_bwd_f32: workspace %zu bytes < %zu", workspace_bytes, need);
     hipStream_t st = as_stream(stream);
@@ -366,8 +311,7 @@ int papc_cloud_concat_conv_bwd_f32(const float *dz, const float *y, const float 
     hipLaunchKernelGGL(cc_fold_kernel, dim3((unsigned)cdiv(n_fold, CC_T)), dim3(CC_T), 0, st, part_w, part_s, B, nch, Cout, dw, ldw, s);
     e = check_launch("papc_cloud_concat_conv_bwd_f32: fold");
     if (e != PAPC_OK) return e;
-    const int64_t n_tail = (int64_t)Cout * Cg + (dg ? (int64_t)B * Cg : 0) + (dbias ? Cout : 0);
-    hipLaunchKernelGGL(cc_tail_kernel, dim3((unsigned)cdiv(n_tail, CC_T)), dim3(CC_T), 0, st, s, g, w, ldw, B, Cp, Cg, Cout, dw, dbias, dg);
+    cc_launch_tail(st, s, g, w, ldw, B, Cp, Cg, Cout, dw, dbias, dg);
     return check_launch("papc_cloud_concat_conv_bwd_f32: tail");
 }
 

@@ -23,7 +23,8 @@
 //   NLOAD loads in flight, the sum does not depend on it; a load past the last chunk is left out (nothing is added in its place).
 //     FOLD_FROM_FIRST   fold_jobs_kernel's few-chunk (wide) shape (folds.hip, NLOAD = 8), pg_fold_kernel (smallm.hip),
 //                       ct_fold_kernel (cloud_transform.hip)
-//     FOLD_FROM_ZERO    cc_fold_kernel (cloud_concat.hip): NLOAD = 4 for the weight block, 1 for the per-cloud sums
+//     FOLD_FROM_ZERO    cc_fold_kernel (cloud_concat.hip): NLOAD = 4 for the weight block; cc_fold_s (cloud_concat.h, the per-cloud sums of
+//                       cc_fold_kernel and cck_fold_kernel): NLOAD = 1
 //
 // SLICE TREE  reduce_partials_strided_kernel (folds.hip), its only user: 64 slices, slice sl sums chunks sl, sl + 64, ... to 0.f in
 //   order (a missing chunk adds 0.f), then red[sl] += red[sl + h] for h = 32, 16, ... 1.

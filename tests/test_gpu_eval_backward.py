@@ -305,7 +305,7 @@ def test_flat_params_in_eval_go_through_autograd_and_accumulate(dev, monkeypatch
         assert torch.equal(v, before[k]), k
 
 
-# ---- segment._CloudConcatBnRelu -----------------------------------------------------------------------------------------------------------
+# ---- cloudconcat._CloudConcatBnRelu (through segment.cloud_concat_bn_relu) ----------------------------------------------------------------
 SEG_BAR = 2e-4       # tests/test_gpu_pointnet_seg.py
 # float32-vs-float64 drift of the twin's ReLU decisions on the CPU (concat_f32_drift): cg = 64: 0 of 196608, cg = 128: 0 of 196608, with the
 # edge channels and without

@@ -178,7 +178,7 @@ VIA_AUTOGRAD = {
     "pointnet_basic_clas": _wb("fc", (0, 2, 5)),
     # transform.tnet_fc: the 3 x 3 T-Net's last layer has 9 outputs and runs padded, "the padded node hands autograd every gradient"
     "pointnet_clas": _wb("fc", (0, 2, 5)) | _wb("input_fc", (0, 2, 4)),
-    # ... and segment._CloudConcatBnRelu (seg_net[0..1]) has no accumulate flavour: it always returns dw, db, dgamma, dbeta
+    # ... and cloudconcat._CloudConcatBnRelu (seg_net[0..1]) has no accumulate flavour: it always returns dw, db, dgamma, dbeta
     "pointnet_seg": _wb("input_fc", (0, 2, 4)) | _wb("seg_net", (0, 1)),
     # layers._pad_features: D = 3 feature channels are padded to 4, the first conv weight is a zero-padded view (no leaf Parameter)
     "ssg_seg": {"sa1.mlp_convs.0.weight"},

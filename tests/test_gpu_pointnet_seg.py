@@ -11,7 +11,7 @@ import torch
 from papc_amd import _lib
 from papc_amd import head as H
 from papc_amd.models import PointNet_Basic_Seg, PointNet_Seg
-from tests import pointnet_seg_ref
+from tests import concat_cases, pointnet_seg_ref
 from tests.util import assert_close, copy_into_model, kernel_decisions, seeded_model_state
 
 pytestmark = pytest.mark.gpu
@@ -25,89 +25,12 @@ def _np(t):
 
 # ---- the kernels ------------------------------------------------------------------------------------------------------------------------
 
-def _kernel_case(dev, B, N, cg, seed):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B * N, 64, generator=g)
-    gf = torch.relu(torch.randn(B, cg, generator=g))
-    w = torch.randn(512, 64 + cg, generator=g) / np.sqrt(64 + cg)
-    b = torch.randn(512, generator=g) * 0.1
-    dz = torch.randn(B * N, 512, generator=g)
-    gamma = torch.rand(512, generator=g) + 0.5
-    gamma[::4] *= -1.0
-    beta = torch.randn(512, generator=g) * 0.2
-    c12 = torch.randn(2, 512, generator=g) * 0.1
-    return [t.to(dev) for t in (x, gf, w, b, dz, gamma, beta, c12)]
-
-
-def _fwd(lib, x, gf, w, b, B, N, cg, stats=True):
-    dev = x.device
-    y = torch.empty(B * N, 512, device=dev)
-    cvec = torch.empty(B, 512, device=dev)
-    parts = lib.papc_cloud_concat_conv_parts(B, N)
-    st = torch.empty(parts, 2, 512, device=dev) if stats else None
-    _lib.check(lib.papc_cloud_concat_conv_f32(x.data_ptr(), 64, gf.data_ptr(), w.data_ptr(), _lib.ptr(b), B, N, 64, cg, 512, y.data_ptr(),
-                                              cvec.data_ptr(), _lib.ptr(st), _lib.stream_ptr()), "papc_cloud_concat_conv_f32")
-    return y, st
-
-
-def _bwd(lib, consts, dz, y, x, gf, w, B, N, cg, dx=None, accumulate=0):
-    dev = x.device
-    mean, invstd, scale, shift, c1, c2 = consts
-    out = {"dx": dx if dx is not None else torch.empty(B * N, 64, device=dev), "dw": torch.empty(512, 64 + cg, device=dev),
-           "db": torch.empty(512, device=dev), "dg": torch.empty(B, cg, device=dev), "s": torch.empty(B, 512, device=dev)}
-    nb = lib.papc_cloud_concat_conv_bwd_workspace(B, N, 64, cg, 512)
-    ws = torch.empty(nb, device=dev, dtype=torch.uint8)
-    _lib.check(lib.papc_cloud_concat_conv_bwd_f32(dz.data_ptr(), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                                  c1.data_ptr(), c2.data_ptr(), x.data_ptr(), 64, gf.data_ptr(), w.data_ptr(), B, N, 64, cg, 512,
-                                                  out["dx"].data_ptr(), 64, accumulate, out["dw"].data_ptr(), out["db"].data_ptr(), out["dg"].data_ptr(),
-                                                  out["s"].data_ptr(), ws.data_ptr(), nb, _lib.stream_ptr()), "papc_cloud_concat_conv_bwd_f32")
-    return out
-
-
 @pytest.mark.parametrize("cg", [64, 1024])
 @pytest.mark.parametrize("N", [1000, 1024, 2048])
 @pytest.mark.parametrize("B", [1, 32, 33])
 def test_concat_conv_kernels_vs_f64(dev, B, N, cg):
-    lib = _lib.load()
-    x, gf, w, b, dz, gamma, beta, c12 = _kernel_case(dev, B, N, cg, 1000 * B + N + cg)
-    y, stats = _fwd(lib, x, gf, w, b, B, N, cg)
-    x64, g64, w64, b64 = (t.double() for t in (x, gf, w, b))           # (float64 on the device: the reference products)
-    cat = torch.cat([x64, g64.repeat_interleave(N, 0)], 1)
-    y_ref = cat @ w64.t() + b64
-    tag = "B=%d N=%d Cg=%d" % (B, N, cg)
-    assert_close(_np(y), _np(y_ref), BAR, "concat conv y " + tag)
-    s = stats.double().sum(0)
-    assert_close(_np(s[0]), _np(y_ref.sum(0)), BAR, "sum y " + tag)
-    assert_close(_np(s[1]), _np((y_ref * y_ref).sum(0)), BAR, "sum y^2 " + tag)
-    # the backward, from this layer's BatchNorm constants (batch statistics of the kernel's own y) and the kernel's own y
-    yk = y.double()
-    mean = yk.mean(0)
-    invstd = 1.0 / torch.sqrt(yk.var(0, unbiased=False) + 1e-5)
-    scale = gamma.double() * invstd
-    shift = beta.double() - mean * scale
-    consts = [t.float().contiguous() for t in (mean, invstd, scale, shift, c12[0].double(), c12[1].double())]
-    m32, i32, sc32, sh32, k1, k2 = (t.double() for t in consts)
-    p = torch.where(sc32 * yk + sh32 > 0, dz.double(), torch.zeros_like(yk))
-    dY = sc32 * ((p - k1) - (yk - m32) * i32 * k2)
-    out = _bwd(lib, consts, dz, y, x, gf, w, B, N, cg)
-    s_ref = dY.view(B, N, 512).sum(1)
-    assert_close(_np(out["dx"]), _np(dY @ w64[:, :64]), BAR, "dX_p " + tag)
-    dw_ref = dY.t() @ cat
-    assert_close(_np(out["dw"][:, :64]), _np(dw_ref[:, :64]), BAR, "dW_p " + tag)
-    assert_close(_np(out["dw"][:, 64:]), _np(dw_ref[:, 64:]), BAR, "dW_g " + tag)
-    assert_close(_np(out["db"]), _np(dY.sum(0)), BAR, "d bias " + tag)
-    assert_close(_np(out["s"]), _np(s_ref), BAR, "s " + tag)
-    assert_close(_np(out["dg"]), _np(s_ref @ w64[:, 64:]), BAR, "dg " + tag)
-    # two identical calls: bit-identical (no atomics, fixed-order folds); the accumulate flag adds dX to what the buffer holds
-    again = _bwd(lib, consts, dz, y, x, gf, w, B, N, cg)
-    for k in out:
-        assert torch.equal(out[k], again[k]), k
-    base = torch.randn(B * N, 64, generator=torch.Generator().manual_seed(5)).to(dev)
-    acc = _bwd(lib, consts, dz, y, x, gf, w, B, N, cg, dx=base.clone(), accumulate=1)
-    assert_close(_np(acc["dx"]), _np(base.double() + dY @ w64[:, :64]), BAR, "dX_p accumulated " + tag)
-    # eval mode: no statistics, the same y
-    y2, _ = _fwd(lib, x, gf, w, b, B, N, cg, stats=False)
-    assert torch.equal(y2, y)
+    from papc_amd.segment import FAMILY
+    concat_cases.check_kernels_vs_f64(FAMILY, dev, B, N, 64, cg, 512, 1000 * B + N + cg, BAR, "B=%d N=%d Cg=%d" % (B, N, cg))
 
 
 def test_concat_conv_rejects_other_shapes(dev):

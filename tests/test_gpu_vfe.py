@@ -11,7 +11,7 @@ import torch
 from papc_amd import _lib
 from papc_amd import head as H
 from papc_amd.models import VFE_Clas, VFE_Seg
-from tests import vfe_ref
+from tests import concat_cases, vfe_ref
 from tests.ref_fixtures import SEG_STRIDE, gold, recorded_state
 from tests.util import assert_close, copy_into_model, kernel_decisions, seeded_model_state
 
@@ -27,95 +27,24 @@ def _np(t):
 
 # ---- the kernels ------------------------------------------------------------------------------------------------------------------------
 
-def _kernel_case(dev, B, N, cp, cg, cout, seed):
-    """as test_gpu_pointnet_seg._kernel_case: gamma negative on every fourth channel, random c1 / c2"""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B * N, cp, generator=g)
-    gf = torch.relu(torch.randn(B, cg, generator=g))
-    w = torch.randn(cout, cp + cg, generator=g) / np.sqrt(cp + cg)
-    b = torch.randn(cout, generator=g) * 0.1
-    dz = torch.randn(B * N, cout, generator=g)
-    gamma = torch.rand(cout, generator=g) + 0.5
-    gamma[::4] *= -1.0
-    beta = torch.randn(cout, generator=g) * 0.2
-    c12 = torch.randn(2, cout, generator=g) * 0.1
-    return [t.to(dev) for t in (x, gf, w, b, dz, gamma, beta, c12)]
-
-
-def _fwd(lib, x, gf, w, b, B, N, stats=True):
-    dev = x.device
-    cp, cg, cout = x.shape[1], gf.shape[1], w.shape[0]
-    y = torch.empty(B * N, cout, device=dev)
-    cvec = torch.empty(B, cout, device=dev)
-    parts = lib.papc_cloud_concat_k_parts(B, N)
-    st = torch.empty(parts, 2, cout, device=dev) if stats else None
-    _lib.check(lib.papc_cloud_concat_k_f32(x.data_ptr(), cp, gf.data_ptr(), w.data_ptr(), _lib.ptr(b), B, N, cp, cg, cout, y.data_ptr(),
-                                           cvec.data_ptr(), _lib.ptr(st), _lib.stream_ptr()), "papc_cloud_concat_k_f32")
-    return y, st
-
-
-def _bwd(lib, consts, dz, y, x, gf, w, B, N, dx=None, accumulate=0):
-    dev = x.device
-    cp, cg, cout = x.shape[1], gf.shape[1], w.shape[0]
-    mean, invstd, scale, shift, c1, c2 = consts
-    out = {"dx": dx if dx is not None else torch.empty(B * N, cp, device=dev), "dw": torch.empty(cout, cp + cg, device=dev),
-           "db": torch.empty(cout, device=dev), "dg": torch.empty(B, cg, device=dev), "s": torch.empty(B, cout, device=dev)}
-    nb = lib.papc_cloud_concat_k_bwd_workspace(B, N, cp, cg, cout)
-    assert nb > 0
-    ws = torch.empty(nb, device=dev, dtype=torch.uint8)
-    _lib.check(lib.papc_cloud_concat_k_bwd_f32(dz.data_ptr(), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                               c1.data_ptr(), c2.data_ptr(), x.data_ptr(), cp, gf.data_ptr(), w.data_ptr(), B, N, cp, cg, cout,
-                                               out["dx"].data_ptr(), cp, accumulate, out["dw"].data_ptr(), out["db"].data_ptr(), out["dg"].data_ptr(),
-                                               out["s"].data_ptr(), ws.data_ptr(), nb, _lib.stream_ptr()), "papc_cloud_concat_k_bwd_f32")
-    return out
-
-
 # (B, N): a cloud smaller than a row tile; clouds that straddle 128-row tiles, the last segment of a cloud 72 rows; seven full segments + 104 rows
 @pytest.mark.parametrize("cp,cg,cout", [(256, 256, 64), (256, 1280, 512), (64, 64, 128), (192, 2304, 64)])
 @pytest.mark.parametrize("B,N", [(1, 64), (3, 200), (2, 1000)])
 def test_concat_k_kernels_vs_f64(dev, B, N, cp, cg, cout):
-    lib = _lib.load()
-    x, gf, w, b, dz, gamma, beta, c12 = _kernel_case(dev, B, N, cp, cg, cout, 1000 * B + N + cg + cout)
-    y, stats = _fwd(lib, x, gf, w, b, B, N)
-    x64, g64, w64, b64 = (t.double() for t in (x, gf, w, b))           # (float64 on the device: the reference products)
-    cat = torch.cat([x64, g64.repeat_interleave(N, 0)], 1)
-    y_ref = cat @ w64.t() + b64
+    from papc_amd.vfe import FAMILY
     tag = "B=%d N=%d Cp=%d Cg=%d Cout=%d" % (B, N, cp, cg, cout)
-    assert_close(_np(y), _np(y_ref), BAR, "concat conv y " + tag)
-    s = stats.double().sum(0)
-    assert_close(_np(s[0]), _np(y_ref.sum(0)), BAR, "sum y " + tag)
-    assert_close(_np(s[1]), _np((y_ref * y_ref).sum(0)), BAR, "sum y^2 " + tag)
-    # the backward, from this layer's BatchNorm constants (batch statistics of the kernel's own y) and the kernel's own y
-    yk = y.double()
-    mean = yk.mean(0)
-    invstd = 1.0 / torch.sqrt(yk.var(0, unbiased=False) + 1e-5)
-    scale = gamma.double() * invstd
-    shift = beta.double() - mean * scale
-    consts = [t.float().contiguous() for t in (mean, invstd, scale, shift, c12[0].double(), c12[1].double())]
-    m32, i32, sc32, sh32, k1, k2 = (t.double() for t in consts)
-    p = torch.where(sc32 * yk + sh32 > 0, dz.double(), torch.zeros_like(yk))
-    dY = sc32 * ((p - k1) - (yk - m32) * i32 * k2)
-    out = _bwd(lib, consts, dz, y, x, gf, w, B, N)
-    s_ref = dY.view(B, N, cout).sum(1)
-    assert_close(_np(out["dx"]), _np(dY @ w64[:, :cp]), BAR, "dX_p " + tag)
-    dw_ref = dY.t() @ cat
-    assert_close(_np(out["dw"][:, :cp]), _np(dw_ref[:, :cp]), BAR, "dW_p " + tag)
-    assert_close(_np(out["dw"][:, cp:]), _np(dw_ref[:, cp:]), BAR, "dW_g " + tag)
-    assert_close(_np(out["db"]), _np(dY.sum(0)), BAR, "d bias " + tag)
-    assert_close(_np(out["s"]), _np(s_ref), BAR, "s " + tag)
-    assert_close(_np(out["dg"]), _np(s_ref @ w64[:, cp:]), BAR, "dg " + tag)
-    # two identical calls: bit-identical (no atomics, fixed-order folds); the accumulate flag adds dX to what the buffer holds
-    again = _bwd(lib, consts, dz, y, x, gf, w, B, N)
-    for k in out:
-        assert torch.equal(out[k], again[k]), k
-    y_again, stats_again = _fwd(lib, x, gf, w, b, B, N)
-    assert torch.equal(y_again, y) and torch.equal(stats_again, stats)
-    base = torch.randn(B * N, cp, generator=torch.Generator().manual_seed(5)).to(dev)
-    acc = _bwd(lib, consts, dz, y, x, gf, w, B, N, dx=base.clone(), accumulate=1)
-    assert_close(_np(acc["dx"]), _np(base.double() + dY @ w64[:, :cp]), BAR, "dX_p accumulated " + tag)
-    # eval mode: no statistics, the same y
-    y2, _ = _fwd(lib, x, gf, w, b, B, N, stats=False)
-    assert torch.equal(y2, y)
+    concat_cases.check_kernels_vs_f64(FAMILY, dev, B, N, cp, cg, cout, 1000 * B + N + cg + cout, BAR, tag, repeat_forward=True)
+
+
+def test_both_families_on_a_shape_both_take(dev):
+    """Cp = 64, Cg = 128, Cout = 512, B = 2, N = 130 (a full 128-row segment plus 2 rows per cloud, a row tile that straddles the two clouds):
+    both families hold to float64, and their c is bit-equal -- one kernel (cc_cvec_kernel) serves both"""
+    from papc_amd import segment, vfe
+    B, N, cp, cg, cout = 2, 130, 64, 128, 512
+    assert segment.kernel_ok(cp, cg, cout) and vfe.kernel_ok(cp, cg, cout)
+    cvec = [concat_cases.check_kernels_vs_f64(fam, dev, B, N, cp, cg, cout, 77, BAR, "%s B=2 N=130" % fam.fwd, repeat_forward=True)
+            for fam in (segment.FAMILY, vfe.FAMILY)]
+    assert torch.equal(cvec[0], cvec[1])
 
 
 def test_concat_k_rejects_other_shapes(dev):
@@ -429,7 +358,7 @@ def test_train_step_runs_no_library_gemm(dev, kind):
     gemmish = ("cijk", "gemm", "gemv", "bmm", "matmul", "rocblas", "hipblas", "tensile", "mfma")
     mine = lambda n: "papc::" in n.split("(")[0] or n.startswith("_ZN4papc")      # noqa: E731  (demangled or not)
     ours = [n for n in names if mine(n)]
-    for k in ("cck_fwd_kernel", "cck_cvec_kernel", "cck_wt_kernel", "cck_colsum_kernel", "cck_fold_kernel", "cck_tail_kernel"):
+    for k in ("cck_fwd_kernel", "cc_cvec_kernel", "cck_wt_kernel", "cck_colsum_kernel", "cck_fold_kernel", "cc_tail_kernel"):
         assert any(k in n for n in ours), (k, sorted(names))
     foreign = [n for n in names if not mine(n) and any(s in n.lower() for s in gemmish)]
     assert not foreign, foreign
