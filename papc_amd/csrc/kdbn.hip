@@ -4,7 +4,8 @@
 // Reference: PAPC/models/segment/kdunet/kdunet.py:51-61 (ConvBNReLU :20-39)
 //     x = relu(batch_norm(conv(x)));  x = reshape(x, (-1, F, 3, dim));  x = reshape(x, (-1, F, 3 * dim));
 //     x = index_select(x, axis=2, index=sel + 3 * arange(dim));  x = max(reshape(x, (-1, F, dim / 2, 2)), axis=-1)
-// The select is kdconv.hip's (kdsel.h): pre-pool row n takes channel 3f + k at source point p.  The BatchNorm statistics run over EVERY point
+// The select is kdconv.hip's: pre-pool row n takes channel 3f + k at source point p, and the kernels that walk it (forward, dX, dW and their
+// Cin = 3 twins) run kdlevel.h's bodies, as kdconv.hip's do; this file hands in what the norm adds.  The BatchNorm statistics run over EVERY point
 // and every one of the 3F channels, but the conv is linear in its input rows, so they follow from the moments of the Cin-wide rows
 // x [M = B dim, Cin]:  xm = mean_n x[n],  C = sum_n (x[n] - xm)(x[n] - xm)^T,  T = W C  [3F, Cin]:
 //     mu_c = w_c . xm + b_c     var_c = max(T_c . w_c / M, 0)     rstd_c = 1 / sqrt(var_c + eps)     r_c = gamma_c rstd_c
@@ -21,41 +22,24 @@
 //             reads C by rows).  kb_finalize_kernel: a wave per channel, double sums -> zoff = w . xm, rstd, mu, var; running statistics
 //             momentum * running + (1 - momentum) * batch, the biased variance (models._bn1d, bn_ops.hip).
 //             Eval mode: kb_eval_kernel takes zoff = running_mean - bias, rstd from running_var; the forward kernel is the same.
-//   forward   kb_fwd_kernel: kd_fwd_kernel's wave layout; epilogue zhat = (acc - zoff) rstd, a = gamma zhat + beta, ReLU, pair max.  Writes
+//   forward   kb_fwd_kernel: kd_fwd_acc (kdlevel.h); epilogue zhat = (acc - zoff) rstd, a = gamma zhat + beta, ReLU, pair max.  Writes
 //             out, the winner byte and the winner's zhat (the backward's dgamma needs it; it is never recovered by dividing by gamma).
-//   backward  kb_dw_kernel: kd_dw_kernel with a third sum -> per chunk S [3F, Cin], dbeta [3F], dgamma [3F]; folded in chunk order by
+//   backward  kb_dw_kernel: kd_dw_acc with two row sums -> per chunk S [3F, Cin], dbeta [3F], dgamma [3F]; folded in chunk order by
 //             papc_reduce_partials2_f32.  kb_dwfin_kernel: dW, dgamma, dbeta (d bias = exact zeros, nothing under accumulate) and the
 //             per-channel coefficients r, r dbeta / M, r dgamma rstd / M.  kb_a_kernel: A and v, a wave per 32 x 32 block and slice of the 3F
-//             channels, the slices folded in slice order.  kb_dx_kernel: kd_dx_kernel with r g in place of dy, then Cin more k steps (x - xm) (-A), minus v.
+//             channels, the slices folded in slice order.  kb_dx_kernel: kd_dx_acc with dy = r g, then Cin more k steps (x - xm) (-A), minus v.
 //             No float atomics, every sum in a fixed order: two runs are bit-identical.  In eval mode the norm is a fixed affine map:
 //             dW_c = r_c S_c, d bias_c = r_c dbeta_c, dX is the sparse term alone.
 // Products: bf16x3.h on v_mfma_f32_32x32x16_bf16 (fp32 accuracy, fp32 accumulation) for Cin >= 32; the Cin = 3 first level runs fmaf chains
 // on the vector unit (the *3_kernel twins).  Plain C++ loads and stores only.
-#include "bf16x3.h"
 #include "fold.h"
-#include "kdsel.h"
+#include "kdlevel.h"
 
 namespace papc {
 
-constexpr int KB_T = 256;        // threads of every kernel here (4 waves)
-constexpr int KB_CH = 128;       // rows per S chunk (MFMA kernel)
-constexpr int KB_CH3 = 256;      // rows per S chunk (Cin = 3 kernel)
+constexpr int KB_T = KD_T;       // threads of every kernel here (4 waves)
 constexpr int KB_MCH = 256;      // rows per moments chunk
-
-// the 16-wide k step both operands of which are 8 consecutive floats per lane
-__device__ __forceinline__ floatx16 kb_step(const float (&av)[8], const float (&bv)[8], floatx16 acc)
-{
-    bf16x8 ap[3], bp[3];
-    split8(av, ap);
-    split8(bv, bp);
-    return mfma_bf16x3(ap, bp, acc);
-}
-
-__device__ __forceinline__ void kb_ld8(const float *p, float (&v)[8])
-{
-    const float4 a = kd_ld4(p), b = kd_ld4(p + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
+constexpr int KB_FMAX = 1024;    // the widest level
 
 // ---- moments ------------------------------------------------------------------------------------------------------------------------
 // chunk t (blockIdx.x) = rows 256 t .. + 255; workgroup = 16 columns (blockIdx.y) x 16 slices of 16 rows, each summed in row order, the slices
@@ -109,7 +93,7 @@ __global__ __launch_bounds__(KB_T) void kb_gram_kernel(const float *__restrict__
             av[j] = in ? xr[c1] - m1 : 0.f;
             bv[j] = in ? xr[c2] - m2 : 0.f;
         }
-        acc = kb_step(av, bv, acc);
+        acc = kd_step(av, bv, acc);
     }
     float *pt = part + (int64_t)blockIdx.x * Cin * Cin;
 #pragma unroll
@@ -151,9 +135,9 @@ __global__ __launch_bounds__(KB_T) void kb_t_kernel(const float *__restrict__ w,
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     for (int c0 = 0; c0 < Cin; c0 += 16) {
         float av[8], bv[8];
-        kb_ld8(wr + c0, av);
-        kb_ld8(cr + c0, bv);
-        acc = kb_step(av, bv, acc);
+        kd_ld8(wr + c0, av);
+        kd_ld8(cr + c0, bv);
+        acc = kd_step(av, bv, acc);
     }
 #pragma unroll
     for (int i = 0; i < 16; ++i) tm[(int64_t)(o0 + (i & 3) + 8 * (i >> 2) + 4 * h) * Cin + cb * 32 + r] = acc[i];
@@ -235,58 +219,28 @@ __device__ __forceinline__ void kb_store_pair(float z0, float a0, float z1, floa
     zh[at] = w1 ? z1 : z0;
 }
 
-// wave: rows m0 .. m0 + 31 (blockIdx.x), features 32 fb .. + 31 (fb = 4 blockIdx.y + wave): kd_fwd_kernel's layout
+// wave: rows m0 .. m0 + 31 (blockIdx.x), features 32 fb .. + 31 (fb = 4 blockIdx.y + wave): kd_fwd_acc, then per pair the norm, ReLU and max
 __global__ __launch_bounds__(KB_T) void kb_fwd_kernel(const float *__restrict__ x, int64_t ldx, const int *__restrict__ sel, int64_t ss,
                                                       const float *__restrict__ w, const float *__restrict__ stats, const float *__restrict__ gamma,
                                                       const float *__restrict__ beta, int M, int dim, int Cin, int F, float *__restrict__ out,
                                                       unsigned char *__restrict__ win, float *__restrict__ zh)
 {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
-    const int fb = blockIdx.y * 4 + wv;
+    const int fb = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (fb * 32 >= F) return;
-    const int m0 = blockIdx.x * 32;
-    const unsigned info = kd_row_info(m0 + r, M, dim, sel, ss);
-    const int k = (int)(info >> 30);
-    const float *xr = x + (int64_t)(info & KD_ROW) * ldx + 8 * h;
-    const int f = fb * 32 + r;
-    floatx16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    for (int q = 0; q < 3; ++q) {
-        if (__ballot(k == q) == 0) continue;            // (wave-uniform)
-        const bool mine = k == q;
-        const float *wr = w + (int64_t)(3 * f + q) * Cin + 8 * h;
-        for (int c1 = 0; c1 < Cin; c1 += 32)           // (Cin is a multiple of 32: two k steps' loads in flight)
-#pragma unroll
-        for (int c0 = c1; c0 < c1 + 32; c0 += 16) {
-            float av[8], bv[8];
-            if (mine) kb_ld8(xr + c0, av);
-            else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) av[j] = 0.f;
-            }
-            kb_ld8(wr + c0, bv);
-            acc = kb_step(av, bv, acc);
-        }
-    }
+    const int m0 = blockIdx.x * 32, f = fb * 32 + (threadIdx.x & 31);
+    int k;
+    const floatx16 acc = kd_fwd_acc(x, ldx, sel, ss, w, M, dim, Cin, m0, f, k);
     const KbChan ch[3] = {kb_chan(stats, gamma, beta, 3 * F, 3 * f), kb_chan(stats, gamma, beta, 3 * F, 3 * f + 1), kb_chan(stats, gamma, beta, 3 * F, 3 * f + 2)};
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int row = 8 * g + 4 * h + 2 * t;      // lanes 0..31 hold the planes of rows 0..31
-            const int k0 = __shfl(k, row), k1 = __shfl(k, row + 1);
-            const int m = m0 + row;
-            if (m < M) {                                // (M is even: row m + 1 exists)
-                float z0, a0, z1, a1;
-                kb_affine(acc[4 * g + 2 * t], k0 == 0 ? ch[0] : (k0 == 1 ? ch[1] : ch[2]), z0, a0);
-                kb_affine(acc[4 * g + 2 * t + 1], k1 == 0 ? ch[0] : (k1 == 1 ? ch[1] : ch[2]), z1, a1);
-                kb_store_pair(z0, a0, z1, a1, out, win, zh, (int64_t)(m >> 1) * F + f);
-            }
-        }
+    // (captured by value: by reference, ch is indexed through the closure and lands in scratch)
+    kd_fwd_pairs(acc, k, m0, M, F, f, [=](float acc0, int k0, float acc1, int k1, int64_t at) {
+        float z0, a0, z1, a1;
+        kb_affine(acc0, k0 == 0 ? ch[0] : (k0 == 1 ? ch[1] : ch[2]), z0, a0);
+        kb_affine(acc1, k1 == 0 ? ch[0] : (k1 == 1 ? ch[1] : ch[2]), z1, a1);
+        kb_store_pair(z0, a0, z1, a1, out, win, zh, at);
+    });
 }
 
-// Cin = 3: thread = (output row, feature)
+// Cin = 3: thread = (output row, feature); the fmaf chain starts from w0 x0 (no bias: it cancels in the norm)
 __global__ __launch_bounds__(KB_T) void kb_fwd3_kernel(const float *__restrict__ x, int64_t ldx, const int *__restrict__ sel, int64_t ss,
                                                        const float *__restrict__ w, const float *__restrict__ stats, const float *__restrict__ gamma,
                                                        const float *__restrict__ beta, int M, int dim, int F, float *__restrict__ out,
@@ -298,10 +252,8 @@ __global__ __launch_bounds__(KB_T) void kb_fwd3_kernel(const float *__restrict__
     float z[2], a[2];
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
-        const unsigned info = kd_row_info(2 * om + e, M, dim, sel, ss);
-        const float *xr = x + (int64_t)(info & KD_ROW) * ldx;
-        const int o = 3 * f + (int)(info >> 30);
-        const float *wr = w + (int64_t)o * 3;
+        const float *xr, *wr;
+        const int o = kd_fwd3_row(2 * om + e, M, dim, sel, ss, x, ldx, w, f, xr, wr);
         const float acc = fmaf(wr[2], xr[2], fmaf(wr[1], xr[1], wr[0] * xr[0]));
         kb_affine(acc, kb_chan(stats, gamma, beta, 3 * F, o), z[e], a[e]);
     }
@@ -310,130 +262,28 @@ __global__ __launch_bounds__(KB_T) void kb_fwd3_kernel(const float *__restrict__
 
 // ---- backward: the sparse sums S, dbeta, dgamma ----------------------------------------------------------------------------------------
 // chunk t (blockIdx.x) = rows 128 t .. + 127; wave = one 32 x 32 block (features 32 fb .. , input channels 32 cb ..) of each of the three
-// planes: kd_dw_kernel's layout.  part + t * pld: S [3F, Cin] of the chunk, then dbeta [3F], then dgamma [3F].
+// planes (kd_dw_acc with two row sums).  part + t * pld: S [3F, Cin] of the chunk, then dbeta [3F], then dgamma [3F].
 __global__ __launch_bounds__(KB_T) void kb_dw_kernel(const float *__restrict__ gout, const float *__restrict__ outv, const unsigned char *__restrict__ win,
                                                      const float *__restrict__ zh, const float *__restrict__ x, int64_t ldx, const int *__restrict__ sel,
                                                      int64_t ss, int M, int dim, int Cin, int F, float *__restrict__ part, int64_t pld)
 {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
-    const int ncb = Cin >> 5, id = blockIdx.y * 4 + wv;
+    const int r = threadIdx.x & 31;
+    const int ncb = Cin >> 5, id = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (id >= (F >> 5) * ncb) return;
     const int fb = id / ncb, cb = id - fb * ncb;
-    const int f = fb * 32 + r;
-    const int r0 = blockIdx.x * KB_CH;
     floatx16 acc[3];
-    float dbs[3] = {0.f, 0.f, 0.f}, dgs[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[q][i] = 0.f;
-    for (int ks = 0; ks < KB_CH / 16; ++ks) {
-        const int mb = r0 + ks * 16;
-        if (mb >= M) break;                                        // (wave-uniform)
-        const unsigned info = kd_row_info(mb + (lane & 15), M, dim, sel, ss);     // the 16 rows of this k step, four times over
-        const int kl = (int)(info >> 30);
-        float dyv[8], zv[8], bv[8];
-        int kj[8];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {                              // rows mb + 8h + 2t, + 1 = pooled row (mb + 8h) / 2 + t
-            const int mr = mb + 8 * h + 2 * t;
-            float g = 0.f, z = 0.f;
-            unsigned wb = 0;
-            if (mr < M) {
-                const int64_t at = (int64_t)(mr >> 1) * F + f;
-                g = outv[at] > 0.f ? gout[at] : 0.f;
-                z = zh[at];
-                wb = win[at];
-            }
-            dyv[2 * t] = wb == 0 ? g : 0.f;
-            dyv[2 * t + 1] = wb == 0 ? 0.f : g;
-            zv[2 * t] = zv[2 * t + 1] = z;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const unsigned inf = (unsigned)__shfl((int)info, 8 * h + j);
-            kj[j] = (int)(inf >> 30);
-            bv[j] = kj[j] < 3 ? x[(int64_t)(inf & KD_ROW) * ldx + cb * 32 + r] : 0.f;
-        }
-        bf16x8 bp[3];
-        split8(bv, bp);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            if (__ballot(kl == q) == 0) continue;
-            float am[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) am[j] = kj[j] == q ? dyv[j] : 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                dbs[q] += am[j];
-                dgs[q] = fmaf(am[j], zv[j], dgs[q]);
-            }
-            bf16x8 ap[3];
-            split8(am, ap);
-            acc[q] = mfma_bf16x3(ap, bp, acc[q]);
-        }
-    }
-    float *pt = part + (int64_t)blockIdx.x * pld;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int fr = fb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-            pt[(int64_t)(3 * fr + q) * Cin + cb * 32 + r] = acc[q][i];
-        }
-        const float tb = dbs[q] + __shfl_xor(dbs[q], 32), tg = dgs[q] + __shfl_xor(dgs[q], 32);     // the two row halves of the lane pair
-        if (cb == 0 && h == 0) {
-            pt[(int64_t)3 * F * Cin + 3 * f + q] = tb;
-            pt[(int64_t)3 * F * Cin + 3 * F + 3 * f + q] = tg;
-        }
-    }
+    float sums[2][3];                                              // dbeta, dgamma
+    kd_dw_acc<2>(gout, outv, win, zh, x, ldx, sel, ss, M, dim, F, blockIdx.x * KD_CH, fb * 32 + r, cb * 32 + r, acc, sums);
+    kd_dw_store<2>(acc, sums, part + (int64_t)blockIdx.x * pld, Cin, F, fb, cb);
 }
 
-// Cin = 3: chunk t = rows 256 t .. + 255; workgroup = 32 features (blockIdx.y) x 8 slices of the chunk's pooled rows (kd_dw3_kernel's layout).
+// Cin = 3: chunk t = rows 256 t .. + 255; workgroup = 32 features (blockIdx.y) x 8 slices of the chunk's pooled rows (kd_dw3_chunk, 5 sums per plane)
 __global__ __launch_bounds__(KB_T) void kb_dw3_kernel(const float *__restrict__ gout, const float *__restrict__ outv, const unsigned char *__restrict__ win,
                                                       const float *__restrict__ zh, const float *__restrict__ x, int64_t ldx, const int *__restrict__ sel,
                                                       int64_t ss, int M, int dim, int F, float *__restrict__ part, int64_t pld)
 {
     __shared__ float red[8][15][32];
-    const int fl = threadIdx.x & 31, sl = threadIdx.x >> 5;
-    const int f = blockIdx.y * 32 + fl;
-    const int om0 = blockIdx.x * (KB_CH3 / 2);
-    float a[15];
-#pragma unroll
-    for (int i = 0; i < 15; ++i) a[i] = 0.f;
-    for (int i = sl; i < KB_CH3 / 2; i += 8) {
-        const int om = om0 + i;
-        if (2 * om >= M) break;
-        const int64_t at = (int64_t)om * F + f;
-        const float g = outv[at] > 0.f ? gout[at] : 0.f, z = zh[at];
-        const unsigned info = kd_row_info(2 * om + (win[at] ? 1 : 0), M, dim, sel, ss);
-        const int k = (int)(info >> 30);
-        const float *xr = x + (int64_t)(info & KD_ROW) * ldx;
-        const float x0 = xr[0], x1 = xr[1], x2 = xr[2];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const float d = k == q ? g : 0.f;
-            a[5 * q] = fmaf(d, x0, a[5 * q]);
-            a[5 * q + 1] = fmaf(d, x1, a[5 * q + 1]);
-            a[5 * q + 2] = fmaf(d, x2, a[5 * q + 2]);
-            a[5 * q + 3] += d;
-            a[5 * q + 4] = fmaf(d, z, a[5 * q + 4]);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 15; ++i) red[sl][i][fl] = a[i];
-    __syncthreads();
-    if (sl != 0) return;
-    float *pt = part + (int64_t)blockIdx.x * pld;
-#pragma unroll
-    for (int i = 0; i < 15; ++i) {
-        float s = a[i];
-#pragma unroll
-        for (int g = 1; g < 8; ++g) s += red[g][i][fl];
-        const int q = i / 5, c = i - 5 * q;
-        if (c < 3) pt[(int64_t)(3 * f + q) * 3 + c] = s;
-        else pt[(int64_t)3 * F * 3 + (c - 3) * 3 * F + 3 * f + q] = s;
-    }
+    kd_dw3_chunk<2>(gout, outv, win, zh, x, ldx, sel, ss, M, dim, F, blockIdx.x * (KD_CH3 / 2), blockIdx.y * 32, red, part + (int64_t)blockIdx.x * pld);
 }
 
 // thread = element (o, c) of dW; the c = 0 thread of a channel also writes dgamma, dbeta, the zero bias gradient and the coefficients
@@ -491,7 +341,7 @@ __global__ __launch_bounds__(KB_T) void kb_a_kernel(const float *__restrict__ w,
             bv[j] = wr[cb2 * 32 + r];
             vs = fmaf(d[o], bv[j], vs);
         }
-        acc = kb_step(av, bv, acc);
+        acc = kd_step(av, bv, acc);
     }
     float *am = part + (int64_t)blockIdx.y * ((int64_t)Cin * Cin + Cin);
 #pragma unroll
@@ -519,69 +369,41 @@ __global__ __launch_bounds__(64) void kb_a3_kernel(const float *__restrict__ w, 
 }
 
 // ---- backward: dX -------------------------------------------------------------------------------------------------------------------
-// wave: source rows m0 .. m0 + 31, input channels 32 cb .. + 31 (kd_dx_kernel's layout).  A[row r][f] = r_c g[row fed by r through plane q][f],
-// B[f][col r] = W[3f + q][32 cb + r]; dense: A[row r][c] = x[m0 + r][c] - xm[c], B[c][col r] = -A[32 cb + r][c] (A's triangles agree to
-// rounding), and v is subtracted in the epilogue.
+// dy of a selected winner with out > 0: the pooled gradient times r_c (coef's first block), c = 3f + q
+struct KbDyScaled {
+    const float *r;
+    __device__ __forceinline__ float operator()(float g, int c) const { return g * r[c]; }
+};
+
+// wave: source rows m0 .. m0 + 31 (blockIdx.x), input channels 32 cb .. + 31 (cb = 4 blockIdx.y + wave): kd_dx_acc with dy = r_c g; then the
+// dense term in the same accumulator, A[row r][c] = x[m0 + r][c] - xm[c], B[c][col r] = -A[32 cb + r][c] (A's triangles agree to rounding),
+// and v is subtracted in the epilogue.
 __global__ __launch_bounds__(KB_T) void kb_dx_kernel(const float *__restrict__ gout, const float *__restrict__ outv, const unsigned char *__restrict__ win,
                                                      const int *__restrict__ sel, int64_t ss, const float *__restrict__ w, const float *__restrict__ coef,
                                                      const float *__restrict__ x, int64_t ldx, const float *__restrict__ mean, const float *__restrict__ am,
                                                      const float *__restrict__ v, int dense, int M, int dim, int Cin, int F, float *__restrict__ dx,
                                                      int64_t ldd)
 {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
-    const int cb = blockIdx.y * 4 + wv;
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int cb = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (cb * 32 >= Cin) return;
     const int m0 = blockIdx.x * 32, m = m0 + r;
     const bool live = m < M;
-    const int b = live ? m / dim : 0, p = live ? m - b * dim : 0;
-    floatx16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    for (int q = 0; q < 3; ++q) {
-        int n = 0;
-        const bool vq = live && kd_fed_row(b, p, q, dim, sel, ss, n);
-        if (__ballot(vq) == 0) continue;
-        const int64_t at = (((int64_t)b * dim + n) >> 1) * F + 8 * h;      // (b dim is even)
-        const unsigned par = (unsigned)(n & 1);
-        const float *wq = w + (int64_t)(3 * 8 * h + q) * Cin + cb * 32 + r;
-        const float *rq = coef + 3 * 8 * h + q;
-        for (int f1 = 0; f1 < F; f1 += 32)             // (F is a multiple of 32: two k steps' loads in flight)
-#pragma unroll
-        for (int f0 = f1; f0 < f1 + 32; f0 += 16) {
-            float av[8], bv[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) bv[j] = wq[(int64_t)3 * (f0 + j) * Cin];
-            if (vq) {
-                float g[8], o[8];
-                kb_ld8(gout + at + f0, g);
-                kb_ld8(outv + at + f0, o);
-                const uint2 wb = *reinterpret_cast<const uint2 *>(win + at + f0);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const unsigned wj = ((j < 4 ? wb.x : wb.y) >> (8 * (j & 3))) & 0xffu;
-                    av[j] = (o[j] > 0.f && wj == par) ? g[j] * rq[3 * (f0 + j)] : 0.f;
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) av[j] = 0.f;
-            }
-            acc = kb_step(av, bv, acc);
-        }
-    }
+    floatx16 acc = kd_dx_acc(gout, outv, win, sel, ss, w, M, dim, Cin, F, m0, cb, KbDyScaled{coef});
     float vc = 0.f;
     if (dense) {
         const float *xr = x + (int64_t)(live ? m : 0) * ldx + 8 * h, *ar = am + (int64_t)(cb * 32 + r) * Cin + 8 * h, *mr = mean + 8 * h;
         for (int c0 = 0; c0 < Cin; c0 += 16) {
             float av[8], bv[8], mv[8];
-            kb_ld8(xr + c0, av);
-            kb_ld8(mr + c0, mv);
-            kb_ld8(ar + c0, bv);
+            kd_ld8(xr + c0, av);
+            kd_ld8(mr + c0, mv);
+            kd_ld8(ar + c0, bv);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 av[j] = live ? av[j] - mv[j] : 0.f;
                 bv[j] = -bv[j];
             }
-            acc = kb_step(av, bv, acc);
+            acc = kd_step(av, bv, acc);
         }
         vc = v[cb * 32 + r];
     }
@@ -600,54 +422,26 @@ __global__ __launch_bounds__(KB_T) void kb_dx3_kernel(const float *__restrict__ 
 {
     const int m = blockIdx.x * KB_T + threadIdx.x;
     if (m >= M) return;
-    const int b = m / dim, p = m - b * dim;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-    for (int q = 0; q < 3; ++q) {
-        int n;
-        if (!kd_fed_row(b, p, q, dim, sel, ss, n)) continue;
-        const int64_t at = (((int64_t)b * dim + n) >> 1) * F;
-        const unsigned par = (unsigned)(n & 1);
-        for (int f = 0; f < F; ++f) {
-            const float d = (outv[at + f] > 0.f && win[at + f] == par) ? gout[at + f] * coef[3 * f + q] : 0.f;
-            const float *wr = w + (int64_t)(3 * f + q) * 3;
-            a0 = fmaf(d, wr[0], a0);
-            a1 = fmaf(d, wr[1], a1);
-            a2 = fmaf(d, wr[2], a2);
-        }
-    }
+    float a[3] = {0.f, 0.f, 0.f};
+    kd_dx3_acc(gout, outv, win, sel, ss, w, m, dim, F, a, KbDyScaled{coef});
     if (dense) {
         const float *xr = x + (int64_t)m * ldx;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float t = xr[c] - mean[c];
-            a0 = fmaf(-t, am[3 * c], a0);
-            a1 = fmaf(-t, am[3 * c + 1], a1);
-            a2 = fmaf(-t, am[3 * c + 2], a2);
+            a[0] = fmaf(-t, am[3 * c], a[0]);
+            a[1] = fmaf(-t, am[3 * c + 1], a[1]);
+            a[2] = fmaf(-t, am[3 * c + 2], a[2]);
         }
-        a0 -= v[0]; a1 -= v[1]; a2 -= v[2];
+        a[0] -= v[0]; a[1] -= v[1]; a[2] -= v[2];
     }
     float *o = dx + (int64_t)m * ldd;
-    o[0] = a0; o[1] = a1; o[2] = a2;
+    o[0] = a[0]; o[1] = a[1]; o[2] = a[2];
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------
-static bool kb_ok(int dim, int Cin, int F)
-{
-    return dim >= 2 && dim % 2 == 0 && (Cin == 3 || (Cin >= 32 && Cin <= 512 && Cin % 32 == 0)) && F >= 32 && F <= 1024 && F % 32 == 0;
-}
-
-static int kb_shape_ok(const char *who, int B, int dim, int Cin, int F)
-{
-    PAPC_REQUIRE(dim >= 2 && dim % 2 == 0, PAPC_E_UNSUPPORTED, "%s: dim=%d (points per cloud: even, >= 2)", who, dim);
-    PAPC_REQUIRE(Cin == 3 || (Cin >= 32 && Cin <= 512 && Cin % 32 == 0), PAPC_E_UNSUPPORTED, "%s: Cin=%d (3, or a multiple of 32 up to 512)", who, Cin);
-    PAPC_REQUIRE(F >= 32 && F <= 1024 && F % 32 == 0, PAPC_E_UNSUPPORTED, "%s: F=%d (a multiple of 32 up to 1024)", who, F);
-    PAPC_REQUIRE(B >= 1 && (int64_t)B * dim <= ((int64_t)1 << 28), PAPC_E_INVALID, "%s: B=%d dim=%d (B >= 1, B * dim <= 2^28)", who, B, dim);
-    return PAPC_OK;
-}
-
 static size_t kb_pad4(size_t n) { return (n + 3) & ~(size_t)3; }             // floats: every block of a workspace stays 16-byte aligned
 static int64_t kb_mchunks(int64_t M) { return cdiv(M, KB_MCH); }
-static int64_t kb_chunks(int64_t M, int Cin) { return cdiv(M, Cin == 3 ? KB_CH3 : KB_CH); }
 // kb_a_kernel's slices of the 3F channels: about 2048 waves in all, at least 8 k steps each; 1 = written in place, no fold
 static int kb_a_slices(int Cin, int F)
 {
@@ -662,12 +456,12 @@ using namespace papc;
 
 extern "C" {
 
-int papc_kdbn_ok(int dim, int Cin, int F) { return kb_ok(dim, Cin, F) ? 1 : 0; }
+int papc_kdbn_ok(int dim, int Cin, int F) { return kd_level_ok(dim, Cin, F, KB_FMAX) ? 1 : 0; }
 
 // workspace of the train-mode forward: [column-sum partials | second-moment partials | C]
 size_t papc_kdbn_fwd_workspace(int B, int dim, int Cin, int F)
 {
-    if (B < 1 || !kb_ok(dim, Cin, F) || (int64_t)B * dim > ((int64_t)1 << 28)) return 0;
+    if (B < 1 || !kd_level_ok(dim, Cin, F, KB_FMAX) || (int64_t)B * dim > ((int64_t)1 << 28)) return 0;
     const size_t T = (size_t)kb_mchunks((int64_t)B * dim), cc = (size_t)Cin * Cin;
     return (kb_pad4(T * Cin) + kb_pad4(T * cc) + kb_pad4(cc)) * sizeof(float);
 }
@@ -679,12 +473,10 @@ int papc_kdbn_fwd_f32(const float *x, int64_t ldx, const int32_t *sel, int64_t s
 {
     const char *who = "papc_kdbn_fwd_f32";
     PAPC_REQUIRE(x && sel && w && gamma && beta && out && win && zhat && stats, PAPC_E_INVALID, "%s: null pointer", who);
-    const int err = kb_shape_ok(who, B, dim, Cin, F);
+    int err = kd_level_shape_ok(who, B, dim, Cin, F, KB_FMAX);
     if (err != PAPC_OK) return err;
-    PAPC_REQUIRE(ldx >= Cin && (sel_stride == 0 || sel_stride >= dim), PAPC_E_INVALID, "%s: ldx=%lld < Cin or sel_stride=%lld (0 or >= dim)", who,
-                 (long long)ldx, (long long)sel_stride);
-    PAPC_REQUIRE(Cin == 3 || (ldx % 4 == 0 && aligned16(x) && aligned16(w)), PAPC_E_INVALID, "%s: x and w must be 16-byte aligned, ldx=%lld a multiple of 4",
-                 who, (long long)ldx);
+    err = kd_level_fwd_args_ok(who, x, ldx, sel_stride, w, dim, Cin);
+    if (err != PAPC_OK) return err;
     hipStream_t st = as_stream(stream);
     const int M = B * dim, n_ch = 3 * F;
     if (training) {
@@ -736,8 +528,8 @@ int papc_kdbn_fwd_f32(const float *x, int64_t ldx, const int32_t *sel, int64_t s
 // workspace of the backward: [chunk partials (S | dbeta | dgamma) | S | dbeta, dgamma | coefficients 3 x 3F | A | v | A, v per slice]
 size_t papc_kdbn_bwd_workspace(int B, int dim, int Cin, int F)
 {
-    if (B < 1 || !kb_ok(dim, Cin, F) || (int64_t)B * dim > ((int64_t)1 << 28)) return 0;
-    const size_t T = (size_t)kb_chunks((int64_t)B * dim, Cin), n1 = kb_pad4((size_t)3 * F * Cin), n2 = (size_t)6 * F;
+    if (B < 1 || !kd_level_ok(dim, Cin, F, KB_FMAX) || (int64_t)B * dim > ((int64_t)1 << 28)) return 0;
+    const size_t T = (size_t)kd_level_chunks((int64_t)B * dim, Cin), n1 = kb_pad4((size_t)3 * F * Cin), n2 = (size_t)6 * F;
     const size_t na = kb_pad4((size_t)Cin * Cin) + kb_pad4(Cin), S = (size_t)kb_a_slices(Cin, F);
     return (T * (n1 + n2) + n1 + n2 + (size_t)9 * F + na + (S > 1 ? S * na : 0)) * sizeof(float);
 }
@@ -749,19 +541,16 @@ int papc_kdbn_bwd_f32(const float *gout, const float *out, const uint8_t *win, c
 {
     const char *who = "papc_kdbn_bwd_f32";
     PAPC_REQUIRE(gout && out && win && zhat && x && sel && w && gamma && stats && dw && dgamma && dbeta && workspace, PAPC_E_INVALID, "%s: null pointer", who);
-    const int err = kb_shape_ok(who, B, dim, Cin, F);
+    int err = kd_level_shape_ok(who, B, dim, Cin, F, KB_FMAX);
     if (err != PAPC_OK) return err;
     PAPC_REQUIRE(!training || (mean && tmat), PAPC_E_INVALID, "%s: train mode needs the forward's mean and tmat", who);
-    PAPC_REQUIRE(ldx >= Cin && (sel_stride == 0 || sel_stride >= dim) && (!dx || ldd >= Cin), PAPC_E_INVALID,
-                 "%s: ldx=%lld < Cin, ldd=%lld < Cin or sel_stride=%lld (0 or >= dim)", who, (long long)ldx, (long long)ldd, (long long)sel_stride);
-    PAPC_REQUIRE(Cin == 3 || (aligned16(gout) && aligned16(out) && (reinterpret_cast<uintptr_t>(win) & 7) == 0 && aligned16(x) && ldx % 4 == 0 &&
-                              (!training || aligned16(mean))),
-                 PAPC_E_INVALID, "%s: gout, out, x and mean must be 16-byte aligned, ldx a multiple of 4, the winner bytes 8-byte aligned", who);
-    const size_t need = papc_kdbn_bwd_workspace(B, dim, Cin, F);
-    PAPC_REQUIRE(workspace_bytes >= need && aligned16(workspace), PAPC_E_INVALID, "%s: workspace %zu bytes < %zu (or not 16-byte aligned)", who, workspace_bytes,
-                 need);
+    // (the dense dX term reads x and mean by vector loads)
+    err = kd_level_bwd_args_ok(who, gout, out, win, ldx, sel_stride, dx != nullptr, ldd, dim, Cin, aligned16(x) && ldx % 4 == 0 && (!training || aligned16(mean)),
+                               "gout, out, x and mean must be 16-byte aligned, ldx a multiple of 4, the winner bytes 8-byte aligned", workspace, workspace_bytes,
+                               papc_kdbn_bwd_workspace(B, dim, Cin, F));
+    if (err != PAPC_OK) return err;
     hipStream_t st = as_stream(stream);
-    const int M = B * dim, n_ch = 3 * F, T = (int)kb_chunks(M, Cin), dense = training ? 1 : 0;
+    const int M = B * dim, n_ch = 3 * F, T = (int)kd_level_chunks(M, Cin), dense = training ? 1 : 0;
     const int64_t n1 = (int64_t)kb_pad4((size_t)n_ch * Cin), n2 = (int64_t)2 * n_ch;
     float *part = static_cast<float *>(workspace), *S = part + (int64_t)T * (n1 + n2), *dbg = S + n1, *coef = dbg + n2, *am = coef + 3 * n_ch,
           *v = am + kb_pad4((size_t)Cin * Cin);

@@ -13,6 +13,7 @@ from papc_amd import head as H
 from papc_amd import kdnet
 from papc_amd.models import KDNet
 from tests import kdnet_ref
+from tests.kd_cases import _np, _split_vectors
 from tests.util import assert_close, copy_into_model, seeded_model_state
 
 pytestmark = pytest.mark.gpu
@@ -20,28 +21,10 @@ BAR = 2e-4          # the project's model-level bar (as tests/test_gpu_pointnet.
 NC = 10
 
 
-def _np(t):
-    return t.detach().double().cpu().numpy()
-
-
 # ---- the kernels ------------------------------------------------------------------------------------------------------------------------
 
 SHAPES = [(1024, 3, 32), (512, 32, 64), (64, 128, 128), (32, 128, 256), (8, 256, 512), (4, 512, 512), (2, 512, 128)]
 CASES = [(d, c, f, B) for (d, c, f) in SHAPES for B in (1, 3)] + [(2, 512, 128, 33)]      # dim = 2, B = 33: a ragged last tile over many clouds
-
-
-def _split_vectors(B, dim, seed):
-    """(name, sel) -- sel [dim] (shared by every cloud) or [B, dim]: shared, per cloud, all 0, all 2, and random ones whose rows at n = dim//3 and
-    n = 2 dim//3 (where the weight plane changes) are set to each of 0, 1, 2"""
-    rng = np.random.default_rng(seed)
-    out = [("shared", rng.integers(0, 3, size=dim)), ("per cloud", rng.integers(0, 3, size=(B, dim))),
-           ("all 0", np.zeros(dim, np.int64)), ("all 2", np.full((B, dim), 2))]
-    for v in range(3):
-        s = rng.integers(0, 3, size=(B, dim))
-        s[:, dim // 3] = v
-        s[:, (2 * dim) // 3] = v
-        out.append(("boundary rows = %d" % v, s))
-    return out
 
 
 def _kernel_fwd(lib, x, sel, w, b, B, dim):

@@ -11,7 +11,7 @@ from papc_amd import head as H
 from papc_amd import kdnet
 from papc_amd.models import KDUNet
 from tests import kdunet_ref
-from tests.test_gpu_kdnet import _split_vectors
+from tests.kd_cases import _np, _split_vectors
 from tests.util import assert_close, copy_into_model, kernel_decisions, seeded_model_state
 
 pytestmark = pytest.mark.gpu
@@ -19,10 +19,6 @@ BAR = 2e-4          # the project's model-level bar (as tests/test_gpu_kdnet.py)
 NC = 50
 EPS = kdunet_ref.EPS
 MOM = kdunet_ref.MOMENTUM
-
-
-def _np(t):
-    return t.detach().double().cpu().numpy()
 
 
 # ---- the kernels ------------------------------------------------------------------------------------------------------------------------
@@ -198,6 +194,64 @@ def test_kdbn_clamps_bad_split_values(dev):
     ra, rc = _kernel_bwd(lib, gout, a, x, sel.to(dev), ps[0], ps[2], B, dim), _kernel_bwd(lib, gout, c, x, bad.to(dev), ps[0], ps[2], B, dim)
     for k in ra:
         assert torch.equal(ra[k], rc[k]), k
+
+
+@pytest.mark.parametrize("dim,cin,f,B", [(32, 32, 32, 3),       # M = 96: ragged against the 128-row dW chunk
+                                          (2, 64, 64, 33)])      # M = 66: a ragged last 32-row tile over many clouds; Cin != F
+def test_identity_norm_level_is_kdconv_bit_for_bit(dev, dim, cin, f, B):
+    """With the norm set to the identity a kdbn level is a kdconv level, and the two families run the same bodies (csrc/kdlevel.h): eval mode
+    with eps = 0, running_var = 1, running_mean = bias (zoff = +0 and 1/sigma = 1 exactly), gamma = 1, beta = bias.  (acc - 0) * 1,
+    1 * z + beta and g * 1 are exact, and both dW paths fold the same chunk partials in the same order, so out, win, dX, dW and the bias
+    gradient (kdbn's d bias and its dbeta) equal kdconv's bit for bit.  Cin = 3 is left out on purpose: kdconv starts its fmaf chain from the
+    bias, kdbn from w0 x0 without one, and the two round differently."""
+    lib = _lib.load()
+    assert kdnet.bn_kernel_ok(dim, cin, f) and kdnet.kernel_ok(dim, cin, f)
+    g = torch.Generator().manual_seed(dim * 7 + cin + f + B)
+    M = B * dim
+    x = torch.randn(M, cin, generator=g).to(dev)
+    w = (torch.randn(3 * f, cin, generator=g) / np.sqrt(cin)).to(dev)
+    b = (torch.randn(3 * f, generator=g) * 0.1).to(dev)
+    gout = torch.randn(M // 2, f, generator=g).to(dev)
+    one = torch.ones(3 * f, device=dev)
+    st = _lib.stream_ptr()
+    nan = float("nan")
+    for name, sel in _split_vectors(B, dim, dim + B)[:2]:          # a shared sel [dim] and a per-cloud sel [B, dim]
+        tag = "%s dim=%d Cin=%d F=%d B=%d" % (name, dim, cin, f, B)
+        seld = torch.from_numpy(sel.astype(np.int32)).to(dev)
+        ss = 0 if seld.dim() == 1 else seld.stride(0)
+        # kdconv
+        out_c, win_c = torch.empty(M // 2, f, device=dev), torch.empty(M // 2, f, device=dev, dtype=torch.uint8)
+        _lib.check(lib.papc_kdconv_fwd_f32(x.data_ptr(), cin, seld.data_ptr(), ss, w.data_ptr(), b.data_ptr(), B, dim, cin, f, out_c.data_ptr(),
+                                           win_c.data_ptr(), st), "papc_kdconv_fwd_f32")
+        dx_c, dw_c, db_c = torch.full((M, cin), nan, device=dev), torch.full((3 * f, cin), nan, device=dev), torch.full((3 * f,), nan, device=dev)
+        nb = lib.papc_kdconv_bwd_workspace(B, dim, cin, f)
+        ws = torch.empty(nb, device=dev, dtype=torch.uint8)
+        _lib.check(lib.papc_kdconv_bwd_f32(gout.data_ptr(), out_c.data_ptr(), win_c.data_ptr(), x.data_ptr(), cin, seld.data_ptr(), ss, w.data_ptr(), B,
+                                           dim, cin, f, dx_c.data_ptr(), cin, dw_c.data_ptr(), db_c.data_ptr(), 0, ws.data_ptr(), nb, st),
+                   "papc_kdconv_bwd_f32")
+        # kdbn in eval mode, the norm the identity
+        rmean, rvar = b.clone(), one.clone()
+        out_b, win_b = torch.empty(M // 2, f, device=dev), torch.empty(M // 2, f, device=dev, dtype=torch.uint8)
+        zhat, mean, tmat, stats = (torch.empty(M // 2, f, device=dev), torch.zeros(cin, device=dev), torch.zeros(3 * f, cin, device=dev),
+                                   torch.empty(4, 3 * f, device=dev))
+        nb = lib.papc_kdbn_fwd_workspace(B, dim, cin, f)
+        ws = torch.empty(nb, device=dev, dtype=torch.uint8)
+        _lib.check(lib.papc_kdbn_fwd_f32(x.data_ptr(), cin, seld.data_ptr(), ss, w.data_ptr(), b.data_ptr(), one.data_ptr(), b.data_ptr(),
+                                         rmean.data_ptr(), rvar.data_ptr(), B, dim, cin, f, 0.0, MOM, 0, out_b.data_ptr(), win_b.data_ptr(),
+                                         zhat.data_ptr(), mean.data_ptr(), tmat.data_ptr(), stats.data_ptr(), ws.data_ptr(), nb, st), "papc_kdbn_fwd_f32")
+        assert torch.equal(stats[0], torch.zeros_like(stats[0])) and torch.equal(stats[1], one), "the norm is not the identity " + tag
+        dx_b, dw_b = torch.full((M, cin), nan, device=dev), torch.full((3 * f, cin), nan, device=dev)
+        db_b, dgamma, dbeta = (torch.full((3 * f,), nan, device=dev) for _ in range(3))
+        nb = lib.papc_kdbn_bwd_workspace(B, dim, cin, f)
+        ws = torch.empty(nb, device=dev, dtype=torch.uint8)
+        _lib.check(lib.papc_kdbn_bwd_f32(gout.data_ptr(), out_b.data_ptr(), win_b.data_ptr(), zhat.data_ptr(), x.data_ptr(), cin, seld.data_ptr(), ss,
+                                         w.data_ptr(), one.data_ptr(), mean.data_ptr(), tmat.data_ptr(), stats.data_ptr(), B, dim, cin, f, 0,
+                                         dx_b.data_ptr(), cin, dw_b.data_ptr(), db_b.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), 0, ws.data_ptr(), nb,
+                                         st), "papc_kdbn_bwd_f32")
+        assert float(out_c.abs().max()) > 0 and float(dw_c.abs().max()) > 0 and float(dx_c.abs().max()) > 0, tag
+        for what, got, want in (("out", out_b, out_c), ("win", win_b, win_c), ("dX", dx_b, dx_c), ("dW", dw_b, dw_c), ("d bias", db_b, db_c),
+                                ("dbeta", dbeta, db_c)):
+            assert torch.equal(got, want), "%s of the identity-norm kdbn level differs from kdconv's, %s" % (what, tag)
 
 
 def test_shapes_outside_kdbn_ok(dev):
