@@ -588,6 +588,41 @@ int papc_pfn_bwd_finalize_f32(const float *sums, int64_t M, const float *w, int 
                               papc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The PointPillars detection loss (pointpillars/models/detectors/pointpillars.py:150-213, 468-585 on core/losses.py:151-183, 185-189,
+ * 253-292, 370-391): loss, reduced by-products and the three gradients for upstream gradient 1 in three launches (csrc/detloss.hip).
+ *   box_preds / reg_targets [B,A,7], cls_preds [B,A,C], dir_preds [B,A,2] (has_dir), anchors [B,A,7] (has_dir: only [...,6] is read),
+ *   labels [B,A] int32 (labels_i64: int64): < 0 don't care, 0 negative, k > 0 class k.  All contiguous.
+ *   out [8]: loss, loc_loss_reduced, cls_loss_reduced, dir_loss_reduced (sum / B, without dir_weight), cls_pos_loss / pos_cls_weight,
+ *            cls_neg_loss / neg_cls_weight, 0, 0
+ *   dbox [B,A,7], dcls [B,A,C], ddir [B,A,2] (has_dir): d loss / d prediction
+ *   cls_loss [B,A,C], loc_loss [B,A,7]: the per-anchor losses, cared [B,A] bytes (labels >= 0) -- each optional (NULL: not written)
+ *   workspace: papc_det_loss_workspace bytes; its first 2 B int32 are the per-sample (positives, negatives) counts afterwards.
+ * Sums are per-workgroup partials folded in a fixed order (csrc/fold.h): the same inputs give the same bits.  No host synchronisation.
+ * PAPC_E_UNSUPPORTED: C > 8, code_size != 7, encode_background_as_zeros == 0, codewise == 0. */
+#define PAPC_DET_NORM_BY_NUM_EXAMPLES 0
+#define PAPC_DET_NORM_BY_NUM_POSITIVES 1
+#define PAPC_DET_NORM_BY_NUM_POS_NEG 2
+typedef struct papc_det_loss_desc {
+    int32_t B, A, C, code_size;
+    int32_t norm_type, has_alpha, sin_diff, has_dir;
+    int32_t encode_background_as_zeros, codewise, labels_i64, reserved;
+    float pos_cls_weight, neg_cls_weight, alpha, gamma, sigma;
+    float code_weights[7];
+    float loc_weight, cls_weight, dir_weight;
+} papc_det_loss_desc;
+typedef struct papc_det_loss_io {
+    const float *box_preds, *cls_preds, *dir_preds;
+    const void *labels;
+    const float *reg_targets, *anchors;
+    float *out, *dbox, *dcls, *ddir;
+    float *cls_loss, *loc_loss;
+    uint8_t *cared;
+    void *workspace;
+} papc_det_loss_io;
+int papc_det_loss_workspace(const papc_det_loss_desc *desc, int64_t *bytes);
+int papc_det_loss_fwd_f32(const papc_det_loss_desc *desc, const papc_det_loss_io *io, papc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Harness helpers (the reference's Adam step, PAPC/train.py:62-65,113-116, on one flat buffer)
  * ---------------------------------------------------------------------------------------------- */
 /* ------------------------------------------------------------------------------------------------

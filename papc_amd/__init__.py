@@ -15,6 +15,9 @@ Public surface mirrors the reference:
                           down level (the same behind a BatchNorm whose statistics come from the input rows' moments)
   papc_amd.voxnet      <- the VoxNet backbone (two 3-D convs as implicit GEMMs, the norm on load, the pool in registers), the head's LeakyReLU +
                           dropout and the occupancy grid of a cloud
+  papc_amd.detloss     <- the training branch of PointPillars.forward (detectors/pointpillars.py:150-213): prepare_loss_weights, create_loss,
+                          add_sin_difference, _get_pos_neg_loss, get_direction_target and pointpillars_loss, the whole detection loss with its
+                          three gradients as one autograd node
   papc_amd.datasets    <- PAPC/datasets loaders: PNClasDataLoader / PNSegDataLoader / KDClasDataLoader / KDSegDataLoader / VoxDataLoader
 The compute lives in libpapc_hip.so (hand-written HIP, C ABI in include/papc_hip.h).
 """
