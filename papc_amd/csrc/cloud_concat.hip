@@ -19,6 +19,7 @@
 // Products: v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation: the PAPC_GEMM_F32 arithmetic of papc_mlp_gemm_f32).  At
 // K = 64 the layer is bound by the [M, Cout] traffic of y and dY, not by the matrix rate.  The small per-cloud products are fmaf chains
 // in ascending index order.  Plain C++ loads and stores only.
+#include "carve.h"
 #include "cloud_concat.h"
 
 namespace papc {
@@ -253,6 +254,16 @@ static int cc_shape_ok(const char *who, int B, int N, int Cp, int Cg, int Cout)
 
 static int64_t cc_chunks(int N) { return cdiv(N, CC_BM); }
 
+// workspace of the backward: [dW_p partials per chunk | column-sum partials per chunk | s]
+struct CcBwdPtrs { float *part_w, *part_s, *s; };
+static size_t cc_bwd_layout(int B, int N, int Cout, void *base, CcBwdPtrs &p)
+{
+    WsCarver c{static_cast<char *>(base), 0, 16};
+    const size_t T = (size_t)B * (size_t)cc_chunks(N);
+    p.part_w = c.take<float>(T * Cout * CC_CP); p.part_s = c.take<float>(T * Cout); p.s = c.take<float>((size_t)B * Cout);
+    return c.off;
+}
+
 }  // namespace papc
 
 using namespace papc;
@@ -281,8 +292,8 @@ int papc_cloud_concat_conv_f32(const float *x, int64_t ldx, const float *g, cons
 size_t papc_cloud_concat_conv_bwd_workspace(int B, int N, int Cp, int Cg, int Cout)
 {
     if (B < 1 || N < 1 || Cp != CC_CP || Cout != 512 || Cg < 64 || Cg > 1024 || Cg % 64) return 0;
-    const size_t T = (size_t)B * (size_t)cc_chunks(N);
-    return (T * (size_t)Cout * CC_CP + T * (size_t)Cout + (size_t)B * Cout) * sizeof(float);
+    CcBwdPtrs p;
+    return cc_bwd_layout(B, N, Cout, nullptr, p);
 }
 
 int papc_cloud_concat_conv_bwd_f32(const float *dz, const float *y, const float *mean, const float *invstd, const float *scale, const float *shift,
@@ -293,16 +304,14 @@ int papc_cloud_concat_conv_bwd_f32(const float *dz, const float *y, const float 
     const int err = cc_bwd_args_ok("papc_cloud_concat_conv_bwd_f32", cc_shape_ok, dz, y, mean, invstd, scale, shift, c1, c2, x, ldx, g, w, B, N, Cp, Cg,
                                    Cout, dx, ldd, dw, workspace, true);
     if (err != PAPC_OK) return err;
-    const size_t need = papc_cloud_concat_conv_bwd_workspace(B, N, Cp, Cg, Cout);
+    CcBwdPtrs p;
+    const size_t need = cc_bwd_layout(B, N, Cout, workspace, p);
     PAPC_REQUIRE(workspace_bytes >= need, PAPC_E_INVALID, "papc_cloud_concat_conv_bwd_f32: workspace %zu bytes < %zu", workspace_bytes, need);
     hipStream_t st = as_stream(stream);
     ProfScope prof(PAPC_K_MISC, st);
     const int64_t ldw = (int64_t)Cp + Cg;
     const int nch = (int)cc_chunks(N);
-    const int64_t T = (int64_t)B * nch;
-    float *part_w = static_cast<float *>(workspace);
-    float *part_s = part_w + T * Cout * CC_CP;
-    float *s = s_out ? s_out : part_s + T * Cout;
+    float *part_w = p.part_w, *part_s = p.part_s, *s = s_out ? s_out : p.s;
     hipLaunchKernelGGL(cc_bwd_kernel, dim3((unsigned)nch, (unsigned)B), dim3(CC_T), 0, st, dz, y, mean, invstd, scale, shift, c1, c2, x, ldx, w, ldw, N,
                        Cout, dx, ldd, accumulate, part_w, part_s);
     int e = check_launch("papc_cloud_concat_conv_bwd_f32");

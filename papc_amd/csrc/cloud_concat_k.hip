@@ -22,6 +22,7 @@
 // No float atomics, every cross-workgroup sum a fixed-order fold: two runs are bit-identical.  The small per-cloud products are fmaf chains in
 // ascending index order.  Plain C++ loads and stores; every k loop is straight-line (operands always loaded from addresses that exist, then
 // selected) and cck_drain holds the accumulators over the last MFMA's passes in front of the epilogue.
+#include "carve.h"
 #include "cloud_concat.h"
 
 namespace papc {
@@ -193,22 +194,20 @@ static int cck_shape_ok(const char *who, int B, int N, int Cp, int Cg, int Cout)
 // rows per dW_p range: at most CK_MAX_RANGES ranges, whole multiples of 64 rows, at least 256
 static int64_t cck_rows_per_range(int64_t M) { return std::max<int64_t>(256, cdiv(cdiv(M, CK_MAX_RANGES), 64) * 64); }
 
-struct CckWs { int64_t wt, part, part_ld, ranges, rpr, part_s, s, dxt, total; };   // offsets and sizes in floats
+// workspace of the backward: [W_p^T | dW_p range partials | column-sum partials per segment | s | dense dX]
+struct CckWs { float *wt, *part, *part_s, *s, *dxt; int64_t part_ld, ranges, rpr; };
 
-static CckWs cck_ws(int B, int N, int Cp, int Cout)
+static size_t cck_layout(int B, int N, int Cp, int Cout, void *base, CckWs &l)
 {
-    CckWs l;
+    WsCarver c{static_cast<char *>(base), 0, 16};
     const int64_t M = (int64_t)B * N;
     l.rpr = cck_rows_per_range(M);
     l.ranges = cdiv(M, l.rpr);
     l.part_ld = (int64_t)Cout * Cp + Cout;
-    l.wt = 0;
-    l.part = l.wt + (int64_t)Cp * Cout;
-    l.part_s = l.part + l.ranges * l.part_ld;
-    l.s = l.part_s + (int64_t)B * cdiv(N, CK_BM) * Cout;
-    l.dxt = l.s + (int64_t)B * Cout;
-    l.total = l.dxt + M * Cp;
-    return l;
+    l.wt = c.take<float>((size_t)Cp * Cout); l.part = c.take<float>((size_t)(l.ranges * l.part_ld));
+    l.part_s = c.take<float>((size_t)B * cdiv(N, CK_BM) * Cout); l.s = c.take<float>((size_t)B * Cout);
+    l.dxt = c.take<float>((size_t)M * Cp);
+    return c.off;
 }
 
 }  // namespace papc
@@ -246,7 +245,8 @@ int papc_cloud_concat_k_f32(const float *x, int64_t ldx, const float *g, const f
 size_t papc_cloud_concat_k_bwd_workspace(int B, int N, int Cp, int Cg, int Cout)
 {
     if (B < 1 || N < 1 || B > 65535 || (int64_t)B * N > ((int64_t)1 << 30) || !cck_widths_ok(Cp, Cg, Cout)) return 0;
-    return (size_t)cck_ws(B, N, Cp, Cout).total * sizeof(float);
+    CckWs l;
+    return cck_layout(B, N, Cp, Cout, nullptr, l);
 }
 
 int papc_cloud_concat_k_bwd_f32(const float *dz, const float *y, const float *mean, const float *invstd, const float *scale, const float *shift,
@@ -257,28 +257,26 @@ int papc_cloud_concat_k_bwd_f32(const float *dz, const float *y, const float *me
     const int err = cc_bwd_args_ok("papc_cloud_concat_k_bwd_f32", cck_shape_ok, dz, y, mean, invstd, scale, shift, c1, c2, x, ldx, g, w, B, N, Cp, Cg, Cout,
                                    dx, ldd, dw, workspace, aligned16(workspace));
     if (err != PAPC_OK) return err;
-    const size_t need = papc_cloud_concat_k_bwd_workspace(B, N, Cp, Cg, Cout);
+    CckWs l;
+    const size_t need = cck_layout(B, N, Cp, Cout, workspace, l);
     PAPC_REQUIRE(workspace_bytes >= need, PAPC_E_INVALID, "papc_cloud_concat_k_bwd_f32: workspace %zu bytes < %zu", workspace_bytes, need);
     hipStream_t st = as_stream(stream);
     const int64_t ldw = (int64_t)Cp + Cg;
     const int64_t M = (int64_t)B * N;
     const int nseg = (int)cdiv(N, CK_BM);
-    const CckWs l = cck_ws(B, N, Cp, Cout);
-    float *base = static_cast<float *>(workspace);
-    float *wt = base + l.wt, *part = base + l.part, *part_s = base + l.part_s, *dxt = base + l.dxt;
-    float *s = s_out ? s_out : base + l.s;
+    float *s = s_out ? s_out : l.s;
     int e;
     {
         ProfScope prof(PAPC_K_MISC, st);
         hipLaunchKernelGGL(cck_colsum_kernel, dim3((unsigned)nseg, (unsigned)B), dim3(CC_T), 0, st, dz, y, mean, invstd, scale, shift, c1, c2, N, Cout,
-                           part_s);
+                           l.part_s);
         e = check_launch("papc_cloud_concat_k_bwd_f32: column sums");
         if (e != PAPC_OK) return e;
-        hipLaunchKernelGGL(cck_fold_kernel, dim3((unsigned)cdiv((int64_t)B * Cout, CC_T)), dim3(CC_T), 0, st, part_s, B, nseg, Cout, s);
+        hipLaunchKernelGGL(cck_fold_kernel, dim3((unsigned)cdiv((int64_t)B * Cout, CC_T)), dim3(CC_T), 0, st, l.part_s, B, nseg, Cout, s);
         e = check_launch("papc_cloud_concat_k_bwd_f32: fold");
         if (e != PAPC_OK) return e;
         if (dx) {
-            hipLaunchKernelGGL(cck_wt_kernel, dim3((unsigned)cdiv((int64_t)Cp * Cout, CC_T)), dim3(CC_T), 0, st, w, ldw, Cp, Cout, wt);
+            hipLaunchKernelGGL(cck_wt_kernel, dim3((unsigned)cdiv((int64_t)Cp * Cout, CC_T)), dim3(CC_T), 0, st, w, ldw, Cp, Cout, l.wt);
             e = check_launch("papc_cloud_concat_k_bwd_f32: W_p^T");
             if (e != PAPC_OK) return e;
         }
@@ -289,18 +287,18 @@ int papc_cloud_concat_k_bwd_f32(const float *dz, const float *y, const float *me
     dy.mean = mean; dy.invstd = invstd; dy.scale = scale; dy.shift = shift; dy.c1 = c1; dy.c2 = c2;
     if (dx) {
         const bool direct = !accumulate && ldd == Cp;
-        e = papc_mlp_bwd_dx_f32(&dy, wt, M, Cp, Cout, direct ? dx : dxt, nullptr, nullptr, stream);
+        e = papc_mlp_bwd_dx_f32(&dy, l.wt, M, Cp, Cout, direct ? dx : l.dxt, nullptr, nullptr, stream);
         if (e != PAPC_OK) return e;
         if (!direct) {
             ProfScope prof(PAPC_K_MISC, st);
-            hipLaunchKernelGGL(cck_rows_out_kernel, dim3((unsigned)cdiv(M * Cp, CC_T)), dim3(CC_T), 0, st, dxt, M, Cp, dx, ldd, accumulate);
+            hipLaunchKernelGGL(cck_rows_out_kernel, dim3((unsigned)cdiv(M * Cp, CC_T)), dim3(CC_T), 0, st, l.dxt, M, Cp, dx, ldd, accumulate);
             e = check_launch("papc_cloud_concat_k_bwd_f32: dX rows");
             if (e != PAPC_OK) return e;
         }
     }
-    e = papc_mlp_bwd_dw_f32(&dy, PAPC_A_PLAIN, x, ldx, nullptr, nullptr, nullptr, M, Cp, Cout, (int)l.rpr, part, part + (int64_t)Cout * Cp, l.part_ld, stream);
+    e = papc_mlp_bwd_dw_f32(&dy, PAPC_A_PLAIN, x, ldx, nullptr, nullptr, nullptr, M, Cp, Cout, (int)l.rpr, l.part, l.part + (int64_t)Cout * Cp, l.part_ld, stream);
     if (e != PAPC_OK) return e;
-    e = papc_reduce_partials_strided_f32(part, (int)l.ranges, l.part_ld, Cout, Cp, dw, ldw, 0, stream);
+    e = papc_reduce_partials_strided_f32(l.part, (int)l.ranges, l.part_ld, Cout, Cp, dw, ldw, 0, stream);
     if (e != PAPC_OK) return e;
     ProfScope prof(PAPC_K_MISC, st);
     cc_launch_tail(st, s, g, w, ldw, B, Cp, Cg, Cout, dw, dbias, dg);

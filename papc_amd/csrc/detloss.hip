@@ -10,6 +10,7 @@
 //                     sub-totals of a slot in order, then the scalars
 //
 // No float atomics and no data-dependent order: the same inputs give the same bits.  The counts never leave the device.
+#include "carve.h"
 #include "common.h"
 #include "fold.h"
 
@@ -260,15 +261,18 @@ static int dl_check_desc(const char *who, const papc_det_loss_desc *d)
     return PAPC_OK;
 }
 
-static void dl_geometry(const papc_det_loss_desc *d, DlArgs &a, int64_t &part_off, int64_t &bytes)
+// the launch geometry and the workspace: [counts 2 B, count partials 2 B ncb (one piece) | partial rows]
+static size_t dl_layout(const papc_det_loss_desc *d, void *base, DlArgs &a)
 {
     a.nblk = (int)cdiv(d->A, DL_T);
     a.ncb = (int)cdiv(d->A, DL_CNT);
     a.nrows = d->B * a.nblk;
     a.nchunks = (int)cdiv(a.nrows, DL_ROWS_PER_CHUNK);
-    const int64_t ints = 2 * (int64_t)d->B + 2 * (int64_t)d->B * a.ncb;
-    part_off = cdiv(ints * 4, 16) * 16;
-    bytes = part_off + (int64_t)a.nchunks * 64 * 4;
+    WsCarver c{static_cast<char *>(base), 0, 16};
+    a.counts = c.take<int32_t>(2 * (size_t)d->B + 2 * (size_t)d->B * a.ncb);
+    a.cnt_part = base ? a.counts + 2 * (int64_t)d->B : nullptr;
+    a.part = c.take<float>((size_t)a.nchunks * 64);
+    return c.off;
 }
 
 }  // namespace papc
@@ -281,8 +285,7 @@ extern "C" int papc_det_loss_workspace(const papc_det_loss_desc *desc, int64_t *
     if (rc) return rc;
     PAPC_REQUIRE(bytes, PAPC_E_INVALID, "papc_det_loss_workspace: null pointer");
     DlArgs a;
-    int64_t off;
-    dl_geometry(desc, a, off, *bytes);
+    *bytes = (int64_t)dl_layout(desc, nullptr, a);
     return PAPC_OK;
 }
 
@@ -304,11 +307,7 @@ extern "C" int papc_det_loss_fwd_f32(const papc_det_loss_desc *desc, const papc_
     memset(&a, 0, sizeof(a));
     a.d = *desc;
     a.io = *io;
-    int64_t off, bytes;
-    dl_geometry(desc, a, off, bytes);
-    a.counts = static_cast<int32_t *>(io->workspace);
-    a.cnt_part = a.counts + 2 * (int64_t)desc->B;
-    a.part = reinterpret_cast<float *>(static_cast<char *>(io->workspace) + off);
+    dl_layout(desc, io->workspace, a);
     hipStream_t st = as_stream(stream);
     const dim3 cgrid((unsigned)a.ncb, (unsigned)desc->B);
     const unsigned mgrid = (unsigned)a.nchunks * DL_ROWS_PER_CHUNK;

@@ -32,6 +32,7 @@
 //             dW_c = r_c S_c, d bias_c = r_c dbeta_c, dX is the sparse term alone.
 // Products: bf16x3.h on v_mfma_f32_32x32x16_bf16 (fp32 accuracy, fp32 accumulation) for Cin >= 32; the Cin = 3 first level runs fmaf chains
 // on the vector unit (the *3_kernel twins).  Plain C++ loads and stores only.
+#include "carve.h"
 #include "fold.h"
 #include "kdlevel.h"
 
@@ -450,6 +451,30 @@ static int kb_a_slices(int Cin, int F)
     return std::max(1, std::min(2048 / (ncb * ncb), ks / 8));
 }
 
+// workspace of the train-mode forward: [column-sum partials | second-moment partials | C]; the eval-mode forward takes none
+struct KbFwdPtrs { float *psum, *pgram, *cm; };
+static size_t kb_fwd_layout(int B, int dim, int Cin, bool training, void *base, KbFwdPtrs &p)
+{
+    WsCarver c{static_cast<char *>(base), 0, 16};
+    const size_t T = (size_t)kb_mchunks((int64_t)B * dim), cc = (size_t)Cin * Cin;
+    if (training) { p.psum = c.take<float>(T * Cin); p.pgram = c.take<float>(T * cc); p.cm = c.take<float>(kb_pad4(cc)); }
+    return c.off;
+}
+
+// workspace of the backward: [chunk partials (S | dbeta | dgamma) | S | dbeta, dgamma | coefficients 3 x 3F | A | v | A, v per slice]
+struct KbBwdPtrs { float *part, *S, *dbg, *coef, *am, *v, *apart; int64_t n1, n2; };
+static size_t kb_bwd_layout(int B, int dim, int Cin, int F, void *base, KbBwdPtrs &p)
+{
+    WsCarver c{static_cast<char *>(base), 0, 16};
+    const size_t T = (size_t)kd_level_chunks((int64_t)B * dim, Cin), S = (size_t)kb_a_slices(Cin, F);
+    p.n1 = (int64_t)kb_pad4((size_t)3 * F * Cin); p.n2 = (int64_t)6 * F;
+    p.part = c.take<float>(T * (size_t)(p.n1 + p.n2));
+    p.S = c.take<float>((size_t)p.n1); p.dbg = c.take<float>((size_t)p.n2); p.coef = c.take<float>((size_t)9 * F);
+    p.am = c.take<float>((size_t)Cin * Cin); p.v = c.take<float>(kb_pad4(Cin));
+    p.apart = S > 1 ? c.take<float>(S * ((size_t)Cin * Cin + Cin)) : p.am;       // (slices only for Cin % 32 == 0: unpadded; one: A is written in place)
+    return c.off;
+}
+
 }  // namespace papc
 
 using namespace papc;
@@ -458,12 +483,11 @@ extern "C" {
 
 int papc_kdbn_ok(int dim, int Cin, int F) { return kd_level_ok(dim, Cin, F, KB_FMAX) ? 1 : 0; }
 
-// workspace of the train-mode forward: [column-sum partials | second-moment partials | C]
 size_t papc_kdbn_fwd_workspace(int B, int dim, int Cin, int F)
 {
     if (B < 1 || !kd_level_ok(dim, Cin, F, KB_FMAX) || (int64_t)B * dim > ((int64_t)1 << 28)) return 0;
-    const size_t T = (size_t)kb_mchunks((int64_t)B * dim), cc = (size_t)Cin * Cin;
-    return (kb_pad4(T * Cin) + kb_pad4(T * cc) + kb_pad4(cc)) * sizeof(float);
+    KbFwdPtrs p;
+    return kb_fwd_layout(B, dim, Cin, true, nullptr, p);
 }
 
 int papc_kdbn_fwd_f32(const float *x, int64_t ldx, const int32_t *sel, int64_t sel_stride, const float *w, const float *bias, const float *gamma,
@@ -479,33 +503,33 @@ int papc_kdbn_fwd_f32(const float *x, int64_t ldx, const int32_t *sel, int64_t s
     if (err != PAPC_OK) return err;
     hipStream_t st = as_stream(stream);
     const int M = B * dim, n_ch = 3 * F;
+    KbFwdPtrs p;
+    const size_t need = kb_fwd_layout(B, dim, Cin, training != 0, workspace, p);
     if (training) {
         PAPC_REQUIRE(mean && tmat && workspace, PAPC_E_INVALID, "%s: train mode needs mean, tmat and a workspace", who);
-        const size_t need = papc_kdbn_fwd_workspace(B, dim, Cin, F);
         PAPC_REQUIRE(workspace_bytes >= need && aligned16(workspace) && aligned16(mean) && aligned16(tmat), PAPC_E_INVALID,
                      "%s: workspace %zu bytes < %zu (or workspace / mean / tmat not 16-byte aligned)", who, workspace_bytes, need);
         const int T = (int)kb_mchunks(M);
         const size_t cc = (size_t)Cin * Cin;
-        float *psum = static_cast<float *>(workspace), *pgram = psum + kb_pad4((size_t)T * Cin), *cm = pgram + kb_pad4((size_t)T * cc);
         {
             ProfScope prof(PAPC_K_MISC, st);
-            hipLaunchKernelGGL(kb_colsum_kernel, dim3((unsigned)T, (unsigned)cdiv(Cin, 16)), dim3(KB_T), 0, st, x, ldx, M, Cin, psum);
-            hipLaunchKernelGGL(kb_mean_kernel, dim3((unsigned)cdiv(Cin, KB_T)), dim3(KB_T), 0, st, psum, T, M, Cin, mean);
+            hipLaunchKernelGGL(kb_colsum_kernel, dim3((unsigned)T, (unsigned)cdiv(Cin, 16)), dim3(KB_T), 0, st, x, ldx, M, Cin, p.psum);
+            hipLaunchKernelGGL(kb_mean_kernel, dim3((unsigned)cdiv(Cin, KB_T)), dim3(KB_T), 0, st, p.psum, T, M, Cin, mean);
             if (Cin == 3)
-                hipLaunchKernelGGL(kb_gram3_kernel, dim3((unsigned)T), dim3(KB_T), 0, st, x, ldx, mean, M, pgram);
+                hipLaunchKernelGGL(kb_gram3_kernel, dim3((unsigned)T), dim3(KB_T), 0, st, x, ldx, mean, M, p.pgram);
             else
                 hipLaunchKernelGGL(kb_gram_kernel, dim3((unsigned)T, (unsigned)cdiv((int64_t)(Cin / 32) * (Cin / 32), 4)), dim3(KB_T), 0, st, x, ldx, mean, M,
-                                   Cin, pgram);
+                                   Cin, p.pgram);
             const int e = check_launch("papc_kdbn_fwd_f32: moments");
             if (e != PAPC_OK) return e;
         }
-        int e = papc_reduce_partials_f32(pgram, T, (int64_t)cc, cm, 0, stream);          // the chunks in chunk order (fold.h)
+        int e = papc_reduce_partials_f32(p.pgram, T, (int64_t)cc, p.cm, 0, stream);      // the chunks in chunk order (fold.h)
         if (e != PAPC_OK) return e;
         ProfScope prof(PAPC_K_MISC, st);
         if (Cin == 3)
-            hipLaunchKernelGGL(kb_t3_kernel, dim3((unsigned)cdiv(n_ch, KB_T)), dim3(KB_T), 0, st, w, cm, n_ch, tmat);
+            hipLaunchKernelGGL(kb_t3_kernel, dim3((unsigned)cdiv(n_ch, KB_T)), dim3(KB_T), 0, st, w, p.cm, n_ch, tmat);
         else
-            hipLaunchKernelGGL(kb_t_kernel, dim3((unsigned)(n_ch / 32), (unsigned)cdiv(Cin / 32, 4)), dim3(KB_T), 0, st, w, cm, Cin, tmat);
+            hipLaunchKernelGGL(kb_t_kernel, dim3((unsigned)(n_ch / 32), (unsigned)cdiv(Cin / 32, 4)), dim3(KB_T), 0, st, w, p.cm, Cin, tmat);
         hipLaunchKernelGGL(kb_finalize_kernel, dim3((unsigned)n_ch), dim3(64), 0, st, w, bias, mean, tmat, M, Cin, n_ch, eps, momentum, stats, running_mean,
                            running_var);
         e = check_launch("papc_kdbn_fwd_f32: statistics");
@@ -525,13 +549,11 @@ int papc_kdbn_fwd_f32(const float *x, int64_t ldx, const int32_t *sel, int64_t s
     return check_launch(who);
 }
 
-// workspace of the backward: [chunk partials (S | dbeta | dgamma) | S | dbeta, dgamma | coefficients 3 x 3F | A | v | A, v per slice]
 size_t papc_kdbn_bwd_workspace(int B, int dim, int Cin, int F)
 {
     if (B < 1 || !kd_level_ok(dim, Cin, F, KB_FMAX) || (int64_t)B * dim > ((int64_t)1 << 28)) return 0;
-    const size_t T = (size_t)kd_level_chunks((int64_t)B * dim, Cin), n1 = kb_pad4((size_t)3 * F * Cin), n2 = (size_t)6 * F;
-    const size_t na = kb_pad4((size_t)Cin * Cin) + kb_pad4(Cin), S = (size_t)kb_a_slices(Cin, F);
-    return (T * (n1 + n2) + n1 + n2 + (size_t)9 * F + na + (S > 1 ? S * na : 0)) * sizeof(float);
+    KbBwdPtrs p;
+    return kb_bwd_layout(B, dim, Cin, F, nullptr, p);
 }
 
 int papc_kdbn_bwd_f32(const float *gout, const float *out, const uint8_t *win, const float *zhat, const float *x, int64_t ldx, const int32_t *sel,
@@ -544,34 +566,33 @@ int papc_kdbn_bwd_f32(const float *gout, const float *out, const uint8_t *win, c
     int err = kd_level_shape_ok(who, B, dim, Cin, F, KB_FMAX);
     if (err != PAPC_OK) return err;
     PAPC_REQUIRE(!training || (mean && tmat), PAPC_E_INVALID, "%s: train mode needs the forward's mean and tmat", who);
+    KbBwdPtrs p;
+    const size_t need = kb_bwd_layout(B, dim, Cin, F, workspace, p);
     // (the dense dX term reads x and mean by vector loads)
     err = kd_level_bwd_args_ok(who, gout, out, win, ldx, sel_stride, dx != nullptr, ldd, dim, Cin, aligned16(x) && ldx % 4 == 0 && (!training || aligned16(mean)),
-                               "gout, out, x and mean must be 16-byte aligned, ldx a multiple of 4, the winner bytes 8-byte aligned", workspace, workspace_bytes,
-                               papc_kdbn_bwd_workspace(B, dim, Cin, F));
+                               "gout, out, x and mean must be 16-byte aligned, ldx a multiple of 4, the winner bytes 8-byte aligned", workspace, workspace_bytes, need);
     if (err != PAPC_OK) return err;
     hipStream_t st = as_stream(stream);
     const int M = B * dim, n_ch = 3 * F, T = (int)kd_level_chunks(M, Cin), dense = training ? 1 : 0;
-    const int64_t n1 = (int64_t)kb_pad4((size_t)n_ch * Cin), n2 = (int64_t)2 * n_ch;
-    float *part = static_cast<float *>(workspace), *S = part + (int64_t)T * (n1 + n2), *dbg = S + n1, *coef = dbg + n2, *am = coef + 3 * n_ch,
-          *v = am + kb_pad4((size_t)Cin * Cin);
+    const int64_t n1 = p.n1, n2 = p.n2;
     {
         ProfScope prof(PAPC_K_BWD_DW, st);
         if (Cin == 3)
             hipLaunchKernelGGL(kb_dw3_kernel, dim3((unsigned)T, (unsigned)(F / 32)), dim3(KB_T), 0, st, gout, out, win, zhat, x, ldx, sel, sel_stride, M, dim, F,
-                               part, n1 + n2);
+                               p.part, n1 + n2);
         else
             hipLaunchKernelGGL(kb_dw_kernel, dim3((unsigned)T, (unsigned)cdiv((int64_t)(F / 32) * (Cin / 32), 4)), dim3(KB_T), 0, st, gout, out, win, zhat, x, ldx,
-                               sel, sel_stride, M, dim, Cin, F, part, n1 + n2);
+                               sel, sel_stride, M, dim, Cin, F, p.part, n1 + n2);
         const int e = check_launch("papc_kdbn_bwd_f32: S");
         if (e != PAPC_OK) return e;
     }
     // the chunks in chunk order (fold.h)
-    int e = papc_reduce_partials2_f32(part, T, n1 + n2, n1, S, n2, dbg, 0, stream);
+    int e = papc_reduce_partials2_f32(p.part, T, n1 + n2, n1, p.S, n2, p.dbg, 0, stream);
     if (e != PAPC_OK) return e;
     {
         ProfScope prof(PAPC_K_BWD_DW, st);
-        hipLaunchKernelGGL(kb_dwfin_kernel, dim3((unsigned)cdiv((int64_t)n_ch * Cin, KB_T)), dim3(KB_T), 0, st, S, dbg, stats, gamma, mean, tmat, M, Cin, n_ch,
-                           training ? 0 : 1, accumulate, dw, dbias, dgamma, dbeta, coef);
+        hipLaunchKernelGGL(kb_dwfin_kernel, dim3((unsigned)cdiv((int64_t)n_ch * Cin, KB_T)), dim3(KB_T), 0, st, p.S, p.dbg, stats, gamma, mean, tmat, M, Cin, n_ch,
+                           training ? 0 : 1, accumulate, dw, dbias, dgamma, dbeta, p.coef);
         e = check_launch("papc_kdbn_bwd_f32: dW");
         if (e != PAPC_OK) return e;
     }
@@ -579,33 +600,31 @@ int papc_kdbn_bwd_f32(const float *gout, const float *out, const uint8_t *win, c
     if (dense) {
         int S = 1, ks_per = n_ch / 16;
         const int64_t na = (int64_t)Cin * Cin + Cin;                                           // (v follows A: a slice's layout)
-        float *apart = am;
         {
             ProfScope prof(PAPC_K_BWD_DX, st);
             if (Cin == 3)
-                hipLaunchKernelGGL(kb_a3_kernel, dim3(1), dim3(64), 0, st, w, coef, n_ch, am, v);
+                hipLaunchKernelGGL(kb_a3_kernel, dim3(1), dim3(64), 0, st, w, p.coef, n_ch, p.am, p.v);
             else {
                 ks_per = (int)cdiv(n_ch / 16, kb_a_slices(Cin, F));
                 S = (int)cdiv(n_ch / 16, ks_per);
-                if (S > 1) apart = v + kb_pad4(Cin);
-                hipLaunchKernelGGL(kb_a_kernel, dim3((unsigned)cdiv((int64_t)(Cin / 32) * (Cin / 32), 4), (unsigned)S), dim3(KB_T), 0, st, w, coef, Cin, n_ch,
-                                   ks_per, apart);
+                hipLaunchKernelGGL(kb_a_kernel, dim3((unsigned)cdiv((int64_t)(Cin / 32) * (Cin / 32), 4), (unsigned)S), dim3(KB_T), 0, st, w, p.coef, Cin, n_ch,
+                                   ks_per, p.apart);
             }
             e = check_launch("papc_kdbn_bwd_f32: A");
             if (e != PAPC_OK) return e;
         }
         if (S > 1) {
-            e = papc_reduce_partials_f32(apart, S, na, am, 0, stream);                         // the slices in slice order (fold.h)
+            e = papc_reduce_partials_f32(p.apart, S, na, p.am, 0, stream);                     // the slices in slice order (fold.h)
             if (e != PAPC_OK) return e;
         }
     }
     ProfScope prof(PAPC_K_BWD_DX, st);
     if (Cin == 3)
-        hipLaunchKernelGGL(kb_dx3_kernel, dim3((unsigned)cdiv(M, KB_T)), dim3(KB_T), 0, st, gout, out, win, sel, sel_stride, w, coef, x, ldx, mean, am, v, dense, M,
+        hipLaunchKernelGGL(kb_dx3_kernel, dim3((unsigned)cdiv(M, KB_T)), dim3(KB_T), 0, st, gout, out, win, sel, sel_stride, w, p.coef, x, ldx, mean, p.am, p.v, dense, M,
                            dim, F, dx, ldd);
     else
-        hipLaunchKernelGGL(kb_dx_kernel, dim3((unsigned)cdiv(M, 32), (unsigned)cdiv(Cin / 32, 4)), dim3(KB_T), 0, st, gout, out, win, sel, sel_stride, w, coef, x,
-                           ldx, mean, am, v, dense, M, dim, Cin, F, dx, ldd);
+        hipLaunchKernelGGL(kb_dx_kernel, dim3((unsigned)cdiv(M, 32), (unsigned)cdiv(Cin / 32, 4)), dim3(KB_T), 0, st, gout, out, win, sel, sel_stride, w, p.coef, x,
+                           ldx, mean, p.am, p.v, dense, M, dim, Cin, F, dx, ldd);
     return check_launch("papc_kdbn_bwd_f32: dX");
 }
 

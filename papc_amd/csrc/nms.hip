@@ -9,6 +9,7 @@
 //            on a 64-lane wave the word IS one __ballot over the block's columns
 //   sweep  = the reference's sequential host loop (keep i unless an earlier kept box removed it), one wave on the device
 // IoU in fp32 with the source's "+1" box convention, -ffp-contract=off: the keep decisions are bit-identical to the oracle.
+#include "carve.h"
 #include "common.h"
 #include <rocprim/rocprim.hpp>
 
@@ -307,15 +308,23 @@ using namespace papc;
 
 extern "C" {
 
+// workspace of both drivers: [keys | sorted keys | boxes N x 6 | order | suppression mask N x cb | rocPRIM's temporary storage]
+struct NmsPtrs { uint64_t *keys, *sorted_keys; float *boxes; int32_t *order; unsigned long long *mask; void *tmp; size_t sort_bytes = 0; };
+static size_t nms_layout(int N, void *base, hipStream_t st, NmsPtrs &p)
+{
+    WsCarver c{reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255), 0};     // (the caller's base rounded up: 256 of slack)
+    p.keys = c.take<uint64_t>((size_t)N); p.sorted_keys = c.take<uint64_t>((size_t)N);
+    p.boxes = c.take<float>((size_t)N * 6); p.order = c.take<int32_t>((size_t)N);
+    p.mask = c.take<unsigned long long>((size_t)N * cdiv(N, 64));
+    (void)rocprim::radix_sort_keys_desc(nullptr, p.sort_bytes, p.keys, p.sorted_keys, (size_t)N, 0, 64, st);
+    p.tmp = c.take<char>(p.sort_bytes);
+    return ((c.off + 255) & ~(size_t)255) + 256;
+}
+
 size_t papc_nms_workspace(int N)
 {
-    if (N < 1) return 0;
-    size_t sort_bytes = 0;
-    (void)rocprim::radix_sort_keys_desc(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)N, 0, 64, (hipStream_t)0);
-    const size_t a = 256;
-    auto up = [&](size_t x) { return (x + a - 1) / a * a; };
-    const size_t cb = (size_t)cdiv(N, 64);
-    return up((size_t)N * 8) * 2 + up((size_t)N * 24) + up((size_t)N * 4) + up((size_t)N * cb * 8) + up(sort_bytes) + a;
+    NmsPtrs p;
+    return N < 1 ? 0 : nms_layout(N, nullptr, (hipStream_t)0, p);
 }
 
 static int nms_driver(const float *dets, int N, int W, float thr, int32_t *keep, int32_t *num_out, void *workspace, size_t workspace_bytes,
@@ -323,29 +332,19 @@ static int nms_driver(const float *dets, int N, int W, float thr, int32_t *keep,
 {
     PAPC_REQUIRE(dets && keep && num_out && workspace, PAPC_E_INVALID, "%s: null pointer", who);
     PAPC_REQUIRE(N >= 1 && N <= 65536, PAPC_E_INVALID, "%s: N=%d not in [1, 65536]", who, N);
-    PAPC_REQUIRE(workspace_bytes >= papc_nms_workspace(N), PAPC_E_INVALID, "%s: workspace too small", who);
     hipStream_t st = as_stream(stream);
+    NmsPtrs p;
+    PAPC_REQUIRE(workspace_bytes >= nms_layout(N, workspace, st, p), PAPC_E_INVALID, "%s: workspace too small", who);
     ProfScope prof(PAPC_K_MISC, st);
-    const size_t a = 256;
-    auto up = [&](size_t x) { return (x + a - 1) / a * a; };
     const int cb = cdiv(N, 64);
-    char *w = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace) + a - 1) / a * a);
-    uint64_t *keys = reinterpret_cast<uint64_t *>(w); w += up((size_t)N * 8);
-    uint64_t *sorted_keys = reinterpret_cast<uint64_t *>(w); w += up((size_t)N * 8);
-    float *boxes = reinterpret_cast<float *>(w); w += up((size_t)N * 24);
-    int32_t *order = reinterpret_cast<int32_t *>(w); w += up((size_t)N * 4);
-    unsigned long long *mask = reinterpret_cast<unsigned long long *>(w); w += up((size_t)N * cb * 8);
-    void *tmp = w;
-    size_t sort_bytes = 0;
-    (void)rocprim::radix_sort_keys_desc(nullptr, sort_bytes, keys, sorted_keys, (size_t)N, 0, 64, st);
     const unsigned nb = (unsigned)cdiv(N, 256);
-    hipLaunchKernelGGL(nms_key_kernel, dim3(nb), dim3(256), 0, st, dets, N, W, keys);
+    hipLaunchKernelGGL(nms_key_kernel, dim3(nb), dim3(256), 0, st, dets, N, W, p.keys);
     // descending (score, index): scores.argsort()[::-1] with a stable sort (:145, :469)
-    if (rocprim::radix_sort_keys_desc(tmp, sort_bytes, keys, sorted_keys, (size_t)N, 0, 64, st) != hipSuccess) return check_launch(who);
-    hipLaunchKernelGGL(nms_gather_kernel, dim3(nb), dim3(256), 0, st, dets, sorted_keys, N, W, boxes, order);
-    if (W == 5) hipLaunchKernelGGL(nms_mask_kernel, dim3((unsigned)cb, (unsigned)cb), dim3(64), 0, st, boxes, N, thr, cb, mask);
-    else hipLaunchKernelGGL(rotate_nms_mask_kernel, dim3((unsigned)cb, (unsigned)cb), dim3(64), 0, st, boxes, N, thr, cb, mask);
-    hipLaunchKernelGGL(nms_sweep_kernel, dim3(1), dim3(64), (size_t)cb * 8, st, mask, order, N, cb, keep, num_out);
+    if (rocprim::radix_sort_keys_desc(p.tmp, p.sort_bytes, p.keys, p.sorted_keys, (size_t)N, 0, 64, st) != hipSuccess) return check_launch(who);
+    hipLaunchKernelGGL(nms_gather_kernel, dim3(nb), dim3(256), 0, st, dets, p.sorted_keys, N, W, p.boxes, p.order);
+    if (W == 5) hipLaunchKernelGGL(nms_mask_kernel, dim3((unsigned)cb, (unsigned)cb), dim3(64), 0, st, p.boxes, N, thr, cb, p.mask);
+    else hipLaunchKernelGGL(rotate_nms_mask_kernel, dim3((unsigned)cb, (unsigned)cb), dim3(64), 0, st, p.boxes, N, thr, cb, p.mask);
+    hipLaunchKernelGGL(nms_sweep_kernel, dim3(1), dim3(64), (size_t)cb * 8, st, p.mask, p.order, N, cb, keep, num_out);
     return check_launch(who);
 }
 

@@ -15,6 +15,7 @@
 //      point i = the reference's voxel number of the cell; the point that finds max_voxels cells before it is the break;
 //   4. one thread per segment walks its points: voxel row t = t-th point of the cell with index below the break.
 // Integer / byte work bounded by HBM and the sort; nothing here wants the matrix cores.
+#include "carve.h"
 #include "common.h"
 #include <rocprim/rocprim.hpp>
 
@@ -151,18 +152,25 @@ static int fill_grid(VoxGrid &v, const float *voxel_size, const float *coors_ran
     return *cells < 0xFFFFFFFFll;
 }
 
+// workspace of the voxeliser: [keys in | keys out | flag | before | cut + num | rocPRIM's temporary storage (the sort's or the scan's, the larger)]
+struct VoxPtrs { uint64_t *keys, *sorted; int32_t *flag, *before, *cut; void *tmp; size_t sort_bytes = 0, scan_bytes = 0; };
+static size_t vox_layout(int N, void *base, hipStream_t st, VoxPtrs &p)
+{
+    WsCarver c{reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255), 0};     // (the caller's base rounded up: 256 of slack)
+    p.keys = c.take<uint64_t>((size_t)N); p.sorted = c.take<uint64_t>((size_t)N);
+    p.flag = c.take<int32_t>((size_t)N); p.before = c.take<int32_t>((size_t)N); p.cut = c.take<int32_t>(64);
+    (void)rocprim::radix_sort_keys(nullptr, p.sort_bytes, p.keys, p.sorted, (size_t)N, 0, 64, st);
+    (void)rocprim::exclusive_scan(nullptr, p.scan_bytes, p.flag, p.before, 0, (size_t)N, rocprim::plus<int32_t>(), st);
+    p.tmp = c.take<char>(std::max(p.sort_bytes, p.scan_bytes));
+    return ((c.off + 255) & ~(size_t)255) + 256;
+}
+
 extern "C" {
 
 size_t papc_points_to_voxel_workspace(int N)
 {
-    if (N < 1) return 0;
-    size_t sort_bytes = 0, scan_bytes = 0;
-    (void)rocprim::radix_sort_keys(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)N, 0, 64, (hipStream_t)0);
-    (void)rocprim::exclusive_scan(nullptr, scan_bytes, (int32_t *)nullptr, (int32_t *)nullptr, 0, (size_t)N, rocprim::plus<int32_t>(), (hipStream_t)0);
-    const size_t a = 256;
-    auto up = [&](size_t x) { return (x + a - 1) / a * a; };
-    // keys in, keys out, flag, before, cut+num, rocPRIM temporary storage
-    return up((size_t)N * 8) * 2 + up((size_t)N * 4) * 2 + a + up(std::max(sort_bytes, scan_bytes)) + a;
+    VoxPtrs p;
+    return N < 1 ? 0 : vox_layout(N, nullptr, (hipStream_t)0, p);
 }
 
 int papc_points_to_voxel_f32(const float *points, int N, int ndim, const float *voxel_size, const float *coors_range,
@@ -173,40 +181,28 @@ int papc_points_to_voxel_f32(const float *points, int N, int ndim, const float *
     PAPC_REQUIRE(points && voxel_size && coors_range && voxels && coors && num_points && voxel_num && workspace, PAPC_E_INVALID,
                  "papc_points_to_voxel_f32: null pointer");
     PAPC_REQUIRE(N >= 1 && ndim >= 3 && max_points >= 1 && max_voxels >= 1, PAPC_E_INVALID, "papc_points_to_voxel_f32: bad sizes");
-    PAPC_REQUIRE(workspace_bytes >= papc_points_to_voxel_workspace(N), PAPC_E_INVALID, "papc_points_to_voxel_f32: workspace too small");
+    hipStream_t st = as_stream(stream);
+    VoxPtrs p;
+    PAPC_REQUIRE(workspace_bytes >= vox_layout(N, workspace, st, p), PAPC_E_INVALID, "papc_points_to_voxel_f32: workspace too small");
     VoxGrid v;
     int64_t cells = 0;
     PAPC_REQUIRE(fill_grid(v, voxel_size, coors_range, reverse_index, &cells), PAPC_E_INVALID, "papc_points_to_voxel_f32: bad voxel grid");
-    hipStream_t st = as_stream(stream);
     ProfScope prof(PAPC_K_PFN, st);
-    const size_t a = 256;
-    auto up = [&](size_t x) { return (x + a - 1) / a * a; };
-    char *w = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace) + a - 1) / a * a);
-    uint64_t *keys = reinterpret_cast<uint64_t *>(w); w += up((size_t)N * 8);
-    uint64_t *sorted = reinterpret_cast<uint64_t *>(w); w += up((size_t)N * 8);
-    int32_t *flag = reinterpret_cast<int32_t *>(w); w += up((size_t)N * 4);
-    int32_t *before = reinterpret_cast<int32_t *>(w); w += up((size_t)N * 4);
-    int32_t *cut = reinterpret_cast<int32_t *>(w); w += a;
-    void *tmp = w;
-    size_t sort_bytes = 0, scan_bytes = 0;
-    (void)rocprim::radix_sort_keys(nullptr, sort_bytes, keys, sorted, (size_t)N, 0, 64, st);
-    (void)rocprim::exclusive_scan(nullptr, scan_bytes, flag, before, 0, (size_t)N, rocprim::plus<int32_t>(), st);
-
     const unsigned nb = (unsigned)cdiv(N, 256);
-    if (hipMemsetAsync(flag, 0, (size_t)N * 4, st) != hipSuccess) return check_launch("papc_points_to_voxel_f32: memset");
+    if (hipMemsetAsync(p.flag, 0, (size_t)N * 4, st) != hipSuccess) return check_launch("papc_points_to_voxel_f32: memset");
     if (hipMemsetAsync(voxels, 0, (size_t)max_voxels * max_points * ndim * 4, st) != hipSuccess) return check_launch("papc_points_to_voxel_f32: memset");
     if (hipMemsetAsync(coors, 0, (size_t)max_voxels * 3 * 4, st) != hipSuccess) return check_launch("papc_points_to_voxel_f32: memset");
     if (hipMemsetAsync(num_points, 0, (size_t)max_voxels * 4, st) != hipSuccess) return check_launch("papc_points_to_voxel_f32: memset");
-    if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(cut), N, 1, st) != hipSuccess) return check_launch("papc_points_to_voxel_f32: init");   // no break
-    if (hipMemsetAsync(cut + 1, 0, 4, st) != hipSuccess) return check_launch("papc_points_to_voxel_f32: init");
-    hipLaunchKernelGGL(vox_key_kernel, dim3(nb), dim3(256), 0, st, points, N, ndim, v, keys);
-    if (rocprim::radix_sort_keys(tmp, sort_bytes, keys, sorted, (size_t)N, 0, 64, st) != hipSuccess) return check_launch("papc_points_to_voxel_f32: sort");
-    hipLaunchKernelGGL(vox_mark_kernel, dim3(nb), dim3(256), 0, st, sorted, N, flag);
-    if (rocprim::exclusive_scan(tmp, scan_bytes, flag, before, 0, (size_t)N, rocprim::plus<int32_t>(), st) != hipSuccess) return check_launch("papc_points_to_voxel_f32: scan");
-    hipLaunchKernelGGL(vox_cut_kernel, dim3(nb), dim3(256), 0, st, flag, before, N, max_voxels, cut);
-    hipLaunchKernelGGL(vox_emit_kernel, dim3(nb), dim3(256), 0, st, points, sorted, N, ndim, v, before, cut, max_points, max_voxels, voxels,
+    if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p.cut), N, 1, st) != hipSuccess) return check_launch("papc_points_to_voxel_f32: init");   // no break
+    if (hipMemsetAsync(p.cut + 1, 0, 4, st) != hipSuccess) return check_launch("papc_points_to_voxel_f32: init");
+    hipLaunchKernelGGL(vox_key_kernel, dim3(nb), dim3(256), 0, st, points, N, ndim, v, p.keys);
+    if (rocprim::radix_sort_keys(p.tmp, p.sort_bytes, p.keys, p.sorted, (size_t)N, 0, 64, st) != hipSuccess) return check_launch("papc_points_to_voxel_f32: sort");
+    hipLaunchKernelGGL(vox_mark_kernel, dim3(nb), dim3(256), 0, st, p.sorted, N, p.flag);
+    if (rocprim::exclusive_scan(p.tmp, p.scan_bytes, p.flag, p.before, 0, (size_t)N, rocprim::plus<int32_t>(), st) != hipSuccess) return check_launch("papc_points_to_voxel_f32: scan");
+    hipLaunchKernelGGL(vox_cut_kernel, dim3(nb), dim3(256), 0, st, p.flag, p.before, N, max_voxels, p.cut);
+    hipLaunchKernelGGL(vox_emit_kernel, dim3(nb), dim3(256), 0, st, points, p.sorted, N, ndim, v, p.before, p.cut, max_points, max_voxels, voxels,
                        coors, num_points);
-    if (hipMemcpyAsync(voxel_num, cut + 1, 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return check_launch("papc_points_to_voxel_f32: copy");
+    if (hipMemcpyAsync(voxel_num, p.cut + 1, 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return check_launch("papc_points_to_voxel_f32: copy");
     return check_launch("papc_points_to_voxel_f32");
 }
 
