@@ -164,7 +164,10 @@ typedef struct papc_group_src {
     int64_t sb, sn, sc;
     const float *new_xyz;  /* [B,S,3] */
     const float *feats;    /* [B,N,D] or NULL */
-    const int32_t *idx;    /* [B,S,K] */
+    const int32_t *idx;    /* [B,S,K].  An index outside [0, N) -- the sentinel N a ball query without a hit leaves, -1 -- is a ZERO INPUT ROW for every
+                            * consumer (coordinates and features 0: the row's conv output is the bias): it counts in the BatchNorm statistics and the
+                            * neighbourhood max, sends nothing to grad_feats or the coordinate columns of dW, and is in no point list.  No loader
+                            * follows such an index (held by tests/test_gpu_groupings.py on NaN-guarded buffers). */
     int N, S, K, D;
     int xyz_first;
     /* compacted grouping (papc_compact_plan_f32; all NULL for the padded [B,S,K] lists): point index of every physical row, group of
@@ -915,7 +918,7 @@ int papc_riou_f32(const float *rbboxes, const float *qrbboxes, float standup_thr
  * xyz / new_xyz / idx / N / S / K (feats, D unused); bias may be NULL.  C % 4 == 0.
  * papc_lingather_bwd_f32: from the layer's dense dY source (papc_bwd_dy, DENSE), G [B*N, C] += sum of dY rows per source point
  * (pre-zeroed by the caller, float atomics) and dwx_partial [papc_lingather_parts(M), C, 3] = partial sums of dY^T (xyz_j - centre);
- * with grp->plists (matching the row layout, 256 % (C / 4) == 0): G [B*N, C] = the same sums in fixed order, every row of G WRITTEN (no pre-zeroing),
+ * with grp->plists (matching the row layout, C / 4 <= 64 and 64 % (C / 4) == 0, i.e. C in {4, 8, 16, 32, 64, 128, 256}; PAPC_LG_LISTS != 0): G [B*N, C] = the same sums in fixed order, every row of G WRITTEN (no pre-zeroing),
  * dwx_partial [papc_lingather_list_parts(B * N), C, 3] -- papc_lingather_bwd_parts(grp, B, C) says how many partial rows the call will write;
  * the caller finishes with grad_feats = G W_f, dW_f = G^T feats, dW_x = sum of the partials. */
 int papc_lingather_parts(int64_t M);
@@ -928,6 +931,12 @@ int papc_lingather_parts(int64_t M);
  * to 128 (the last group takes the tail), their exact count}, cidx [cap] point index per row, seg_grp [cap / 8], wrow [cap] = 1 +
  * coef[g] on a group's first row and 1 elsewhere, coef [G] = nsample - rows of the group; cnt8 [G] scratch; cap = G * K rounded up to 128.  Everything
  * stays on the device: consumers take the row count from rows[0] (papc_mlp_gemm_rows_f32, papc_bwd_dy.rows_dev, papc_group_src.rows_dev).
+ * The lists must have the ball query's form: every entry that differs from the first one AHEAD of every repeat of the first one.  The plan counts
+ * the entries that differ from idx[g, 0], rounds up to 8 and keeps that many of the list's first slots BY POSITION; the slots behind are taken to be
+ * copies of the first.  A repeat of the first entry that sits before another entry (or an out-of-range sentinel behind the copies) pushes that entry
+ * out of the kept slots whenever the round-up leaves no room: the neighbour is lost and the first one counted once too often, without an error.
+ * Repeats of a NON-first entry and out-of-range entries among the distinct ones are rows of their own and are handled.  Lists of another form run
+ * padded: the padded kernels and the point lists treat every slot as the row it is (tests/test_gpu_groupings.py, case E6).
  * papc_bn_stats_corr_f32: the copies' share of a layer's statistics -- writes papc_compact_corr_parts() extra partial rows [r][2][C] =
  * sum_g coef[g] (y, y^2)[start[g]] behind the kernel-written rows of stats_partial; papc_bn_finalize_f32 then takes n_tiles + that many
  * rows and M = G * K.
