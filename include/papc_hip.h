@@ -910,6 +910,43 @@ int papc_rbbox_iou_f32(const float *box_corners, const float *qbox_corners, cons
                        float *overlaps, papc_stream_t stream);
 int papc_riou_f32(const float *rbboxes, const float *qrbboxes, float standup_thresh, int N, int K, float *overlaps, papc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * PointPillars predict(): decode, score, top-k and NMS for a whole batch on the device (csrc/detpost.hip).  The non-multiclass
+ * path of pointpillars/models/detectors/pointpillars.py:218-398 with second_box_decode, center_to_corner_box2d, corner_to_standup_nd, nms and
+ * rotate_nms of libs/ops/box_paddle_ops.py, as one launch sequence: score -> per-frame key sort -> gather + decode of the first
+ * min(num_pass, pre_max) ranks -> suppression words -> sweep + emit.  No host synchronisation, no allocation; counts stay on the device.
+ *   ONE ORDER for the top-k cut and the sweep: descending score, on exactly equal scores descending anchor index (papc_nms_f32's order).
+ *   score_mode 0: sigmoid of every column (encode_background_as_zeros); 1: sigmoid, columns 1 onward; 2: softmax, columns 1 onward.  labels
+ *   count from the first scored column; on exactly equal class scores the lowest class wins.  An anchor passes when its mask byte is set
+ *   and (score_thresh <= 0 or score >= score_thresh) in fp32.  dir label = 1 iff dir[1] > dir[0]; the emitted angle is r + pi where
+ *   (r > 0) xor dir label (use_dir).  The NMS box is (x, y, w, l, r) (use_rotate_nms) or the stand-up box of its rotated corners.
+ *   box_preds [B,A,code_size] (code_size 8 iff encode_angle_to_vector, else 7), cls_preds [B,A,num_cls], dir_preds [B,A,2] (use_dir), anchors [A,7]
+ *   (anchor_batch_stride 0) or frame b's at anchors + b * anchor_batch_stride floats, anchors_mask [B,A] bytes or NULL.
+ *   boxes [B,P,7], scores [B,P], labels / dir_labels / anchor_idx [B,P] int32 (anchor_idx in the unmasked numbering), num_det [B],
+ *   num_pass [B] (anchors that passed the threshold, before the top-k cut).  Rows >= num_det[b] are 0, anchor_idx -1: every element is written.
+ * Limits (PAPC_E_INVALID before any launch): 1 <= pre_max <= 4096, 1 <= post_max <= pre_max, 1 <= num_cls <= 16 (>= 2 for modes 1, 2),
+ * 1 <= B <= 65535, A >= 1, B * A < 2^31, score_mode in {0, 1, 2}, code_size against encode_angle_to_vector, null pointers.  papc_det_post_workspace returns (size_t)-1 (and sets the message) for such a desc.
+ * papc_box_decode_f32: second_box_decode (box_paddle_ops.py:48-83) of n boxes, enc [n,code_size], anchors [n,7] -> out [n,7];
+ * code_size is 8 iff encode_angle_to_vector, else 7. */
+typedef struct papc_det_post_desc {
+    int32_t B, A, num_cls, score_mode;
+    int32_t use_dir, use_rotate_nms, encode_angle_to_vector, smooth_dim;
+    int32_t code_size, pre_max, post_max, reserved;
+    float score_thresh, iou_thresh;
+    int64_t anchor_batch_stride;
+} papc_det_post_desc;
+typedef struct papc_det_post_io {
+    const float *box_preds, *cls_preds, *dir_preds, *anchors;
+    const uint8_t *anchors_mask;
+    float *boxes, *scores;
+    int32_t *labels, *dir_labels, *anchor_idx, *num_det, *num_pass;
+} papc_det_post_io;
+size_t papc_det_post_workspace(const papc_det_post_desc *desc);
+int papc_det_post_f32(const papc_det_post_desc *desc, const papc_det_post_io *io, void *workspace, size_t workspace_bytes,
+                      papc_stream_t stream);
+int papc_box_decode_f32(const float *enc, const float *anchors, int64_t n, int code_size, int encode_angle_to_vector, int smooth_dim,
+                        float *out, papc_stream_t stream);
+
 /* First layer of a GROUPED stack with the linear map taken before the gather (pointnet2_basic_layers.py:146-153 + conv1 :215-217):
  * a row is [xyz_j - centre | feats_j], so y[m] = P[j] + W_x (xyz_j - centre) + b with P = feats W_f^T [B*N, C] computed once per
  * SOURCE POINT by the caller (a B*N-row GEMM) instead of once per (group, neighbour) row.

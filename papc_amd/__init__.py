@@ -18,6 +18,8 @@ Public surface mirrors the reference:
   papc_amd.detloss     <- the training branch of PointPillars.forward (detectors/pointpillars.py:150-213): prepare_loss_weights, create_loss,
                           add_sin_difference, _get_pos_neg_loss, get_direction_target and pointpillars_loss, the whole detection loss with its
                           three gradients as one autograd node
+  papc_amd.detect      <- PointPillars.predict (detectors/pointpillars.py:218-398) and second_box_decode: score, top-k, box decode and NMS for a
+                          whole batch as one launch sequence, counts on the device
   papc_amd.datasets    <- PAPC/datasets loaders: PNClasDataLoader / PNSegDataLoader / KDClasDataLoader / KDSegDataLoader / VoxDataLoader
 The compute lives in libpapc_hip.so (hand-written HIP, C ABI in include/papc_hip.h).
 """

@@ -139,6 +139,9 @@ SIGNATURES = {
     "papc_pfn_bwd_finalize_f32": (c_i, [c_p, c_l, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p]),
     "papc_det_loss_workspace": (c_i, [c_p, c_p]),
     "papc_det_loss_fwd_f32": (c_i, [c_p, c_p, c_p]),
+    "papc_det_post_workspace": (ctypes.c_size_t, [c_p]),
+    "papc_det_post_f32": (c_i, [c_p, c_p, c_p, ctypes.c_size_t, c_p]),
+    "papc_box_decode_f32": (c_i, [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p]),
     "papc_points_to_voxel_workspace": (ctypes.c_size_t, [c_i]),
     "papc_points_to_voxel_f32": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, ctypes.c_size_t, c_p]),
     "papc_pillar_scatter_f32": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),

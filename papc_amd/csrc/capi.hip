@@ -174,6 +174,8 @@ int64_t papc_abi_sizeof(const char *struct_name)
     PAPC_SIZEOF(papc_pfn_io)
     PAPC_SIZEOF(papc_det_loss_desc)
     PAPC_SIZEOF(papc_det_loss_io)
+    PAPC_SIZEOF(papc_det_post_desc)
+    PAPC_SIZEOF(papc_det_post_io)
     PAPC_SIZEOF(papc_head_fc_layer)
     PAPC_SIZEOF(papc_head_bwd_job)
     PAPC_SIZEOF(papc_pg_wjob)

@@ -484,7 +484,9 @@ __global__ __launch_bounds__((1 + WS) * WGM * WGN * 64, WS ? (1 + WS) : WGM * WG
 #pragma unroll
                             for (int wi = 0; wi < RB; ++wi) {
                                 const int64_t rb = m0 + (wgm * WM + w0 + wi) * 32 + 4 * hi;
-                                const float *qp = p.rd.y + rb * p.ldy + col;
+                                // (a ragged last tile can END above this wave's first row: rb itself is then past M, and the clamped
+                                // "row 0 of the wave" below would be read up to BM - 1 rows past the end of y -- read the tile's first row)
+                                const float *qp = p.rd.y + ((full || rb < p.M) ? rb : m0) * p.ldy + col;
 #pragma unroll
                                 for (int r = 0; r < 16; ++r) {
                                     const int ro = (r & 3) + 8 * (r >> 2);
