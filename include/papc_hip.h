@@ -389,6 +389,27 @@ typedef struct papc_fold_job {
 } papc_fold_job;
 typedef struct papc_fold_list { papc_fold_job *jobs; int32_t capacity, count; } papc_fold_list;
 int papc_fold_jobs_f32(const papc_fold_job *jobs, int count, papc_stream_t stream);
+/* Two more kinds of list entry, marked by rows < 0 (which the call refused before they existed, so no float job can be mistaken for one).
+ * Only the library appends them (papc_mlp_bwd_dw_max_defer_f32, papc_xyz_l1_bwd_finalize_defer_f32); the layout of papc_fold_job is unchanged.
+ *   rows == PAPC_FOLD_F64Q  the float64 quarter fold (csrc/fold.h): out is a double [cols], out[i] = sum_t partial[t * ld + i]; never accumulates.
+ *   rows == PAPC_FOLD_FIN   a closed-form finalize: this slot is a header and the next n_chunks = PAPC_FOLD_FIN_SLOTS slots of the array hold a
+ *                           papc_fold_fin as raw bytes.  papc_fold_jobs_f32 runs the finalizes of a list behind ALL of its folds (they read what
+ *                           the folds wrote), in list order among themselves and as many per launch as write distinct gradients: a step's
+ *                           list ends in two launches, the folds and the finalizes. */
+#define PAPC_FOLD_F64Q (-1)
+#define PAPC_FOLD_FIN (-2)
+#define PAPC_FIN_DW_MAX 1        /* papc_mlp_bwd_dw_max_f32's closed form: src = its float64 sums */
+#define PAPC_FIN_XYZ_BWD 2       /* papc_xyz_l1_bwd_finalize_f32: src = the float partial rows [parts][C][4] */
+typedef struct papc_fold_fin {
+    int32_t kind, accumulate;
+    int32_t C, parts, ldw, xcol0;
+    double M, inv_m;
+    const void *src;
+    const double *gram;
+    const float *w, *bias, *mean, *invstd, *scale, *e, *c1;
+    float *dgamma, *dbeta, *dw;
+} papc_fold_fin;
+#define PAPC_FOLD_FIN_SLOTS ((int)((sizeof(papc_fold_fin) + sizeof(papc_fold_job) - 1) / sizeof(papc_fold_job)))
 
 /* ------------------------------------------------------------------------------------------------
  * A whole shared-MLP stack in ONE call per direction (csrc/sa_mlp.hip) -- the boundary SURVEY 8b names `papc_sa_mlp_{fwd,bwd}`.
@@ -421,6 +442,7 @@ int papc_fold_jobs_f32(const papc_fold_job *jobs, int count, papc_stream_t strea
 #define PAPC_SA_NO_XYZ_FUSE 256u         /* the dX above a coordinates-only first layer stored + papc_xyz_l1_bwd_f32 instead of papc_mlp_bwd_dx_xyz_f32 */
 #define PAPC_SA_NO_PSEL 1024u           /* compacted max layer: its dX kernel recomputes scale * p per row from gout instead of streaming the reduction's psel */
 #define PAPC_SA_NO_GSIGN 2048u          /* fused group max: both extrema per channel instead of the one sign(gamma) selects */
+#define PAPC_SA_L1_DONE 4096u           /* the forward does NOT launch the coordinates-only first layer's finalize: papc_sa_mlp_xyz1_prep has run on this `saved` */
 #define PAPC_SA_NO_WSTATS 512u          /* compacted stack: unweighted statistics + one papc_bn_stats_corr_f32 launch per layer instead of weighted ones */
 typedef struct papc_sa_desc {
     int32_t B, N, S, K, D;
@@ -486,6 +508,13 @@ typedef struct papc_sa_grads {
 } papc_sa_grads;
 int papc_sa_mlp_plan(const papc_sa_desc *desc, const papc_sa_io *io, papc_sa_plan *plan);
 int papc_sa_mlp_fwd(const papc_sa_plan *plan, const papc_sa_io *io, papc_stream_t stream);
+/* A step that transposes its weights ahead of the forward (papc_transpose_batch_ld_f32: same src / src_ld / dst / rows / cols / copy, count in
+ * [0, 8]) can give that launch the finalize of a coordinates-only first layer to carry, as one extra workgroup: the moments io->xc_gram -> the
+ * layer's BatchNorm constants, running statistics, folded weights and moments in io->saved, exactly what papc_sa_mlp_fwd's own launch of
+ * papc_xyz_l1_finalize_f32 writes (same bits).  Needs plan->xyz1 and io->xc / xc_gram / saved / layer[0]; afterwards papc_sa_mlp_fwd runs on
+ * this plan with PAPC_SA_L1_DONE set in plan->d.disable.  PAPC_XYZ1_RIDE=0: the two launches, transposes then finalize. */
+int papc_sa_mlp_xyz1_prep(const papc_sa_plan *plan, const papc_sa_io *io, const float *const *src, const int *src_ld, float *const *dst,
+                          const int *rows, const int *cols, const int *copy, int count, papc_stream_t stream);
 int papc_sa_mlp_bwd(const papc_sa_plan *plan, const papc_sa_io *io, const papc_sa_grads *grads, papc_stream_t stream);
 
 /* PillarFeatureNet.forward with its single last PFNLayer (PAPC/models/detect/pointpillars/models/bones/pillars.py:79-108 over :29-37; the
@@ -1069,6 +1098,12 @@ int64_t papc_mlp_bwd_dw_max_ws_floats(int64_t M, int Cin, int Cout);
 int papc_mlp_bwd_dw_max_f32(const float *psel, const int32_t *argmax, int K, const float *x, const float *bn_scale, const float *bn_shift,
                             const float *w, const float *e, const float *scale, const float *c1, int64_t M, int Cin, int Cout,
                             float *workspace, float *dw, int accumulate, papc_stream_t stream);
+/* ... with a fold list (papc_sa_grads.defer): only the pass over x is launched; the float64 fold of its chunk partials joins the list's folds
+ * (PAPC_FOLD_F64Q) and the closed form its finalizes (PAPC_FOLD_FIN).  Same bits in dw.  defer == NULL, a full list or PAPC_FOLD_FIN=0: the
+ * three launches of papc_mlp_bwd_dw_max_f32.  workspace, w, e, scale, c1 must stay untouched until papc_fold_jobs_f32 has run. */
+int papc_mlp_bwd_dw_max_defer_f32(const float *psel, const int32_t *argmax, int K, const float *x, const float *bn_scale, const float *bn_shift,
+                                  const float *w, const float *e, const float *scale, const float *c1, int64_t M, int Cin, int Cout,
+                                  float *workspace, float *dw, int accumulate, papc_fold_list *defer, papc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * First layer of a stack fed by coordinates only (sample_and_group with points = None, pointnet2_basic_layers.py:152-153; SA1 of the
@@ -1097,6 +1132,11 @@ int papc_xyz_l1_bwd_f32(const float *dz, const float *xc, const float *wf, int64
 int papc_xyz_l1_bwd_finalize_f32(const float *partial, int parts, int64_t M, int C, const double *gram, const float *w, int ldw, int xcol0,
                                  const float *bias, const float *mean, const float *invstd, const float *scale, float *dgamma, float *dbeta,
                                  float *dw, int accumulate, papc_stream_t stream);
+/* ... with a fold list: nothing is launched, the finalize joins the list's finalizes (PAPC_FOLD_FIN); same bits out.  defer == NULL, a full
+ * list or PAPC_FOLD_FIN=0: papc_xyz_l1_bwd_finalize_f32.  Every input must stay untouched until papc_fold_jobs_f32 has run. */
+int papc_xyz_l1_bwd_finalize_defer_f32(const float *partial, int parts, int64_t M, int C, const double *gram, const float *w, int ldw, int xcol0,
+                                       const float *bias, const float *mean, const float *invstd, const float *scale, float *dgamma, float *dbeta,
+                                       float *dw, int accumulate, papc_fold_list *defer, papc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Stacks with FEW rows (the group_all set-abstraction layer: sample_and_group_all + conv/BN/ReLU x L + max,

@@ -97,6 +97,7 @@ SIGNATURES = {
     "papc_mlp_gemm_rows_w_f32": (c_i, [c_i, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "papc_sa_mlp_plan": (c_i, [c_p, c_p, c_p]),
     "papc_sa_mlp_fwd": (c_i, [c_p, c_p, c_p]),
+    "papc_sa_mlp_xyz1_prep": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p]),
     "papc_sa_mlp_bwd": (c_i, [c_p, c_p, c_p, c_p]),
     "papc_pfn_workspace": (c_i, [c_p, c_p, c_p]),
     "papc_pfn_fwd": (c_i, [c_p, c_p, c_p]),
@@ -205,6 +206,7 @@ SIGNATURES = {
     "papc_mlp_max_nostore_ok": (c_i, [c_l, c_i, c_i, c_i]),
     "papc_mlp_bwd_dw_max_ws_floats": (c_l, [c_l, c_i, c_i]),
     "papc_mlp_bwd_dw_max_f32": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_i, c_p]),
+    "papc_mlp_bwd_dw_max_defer_f32": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_i, c_p, c_p]),
     "papc_mlp_bwd_dx_xyz_ok": (c_i, [c_l, c_i, c_i]),
     "papc_mlp_bwd_dx_xyz_f32": (c_i, [c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p]),
     "papc_mlp_bwd_dx_max_f32": (c_i, [c_p, c_p, c_i, c_p, c_l, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p]),
@@ -216,6 +218,7 @@ SIGNATURES = {
     "papc_xyz_l1_finalize_f32": (c_i, [c_p, c_i, c_l, c_p, c_i, c_i, c_p, c_p, c_p, c_f, c_f, c_i] + [c_p] * 9),
     "papc_xyz_l1_bwd_f32": (c_i, [c_p, c_p, c_p, c_l, c_i, c_p, c_p]),
     "papc_xyz_l1_bwd_finalize_f32": (c_i, [c_p, c_i, c_l, c_i, c_p, c_p, c_i, c_i] + [c_p] * 7 + [c_i, c_p]),
+    "papc_xyz_l1_bwd_finalize_defer_f32": (c_i, [c_p, c_i, c_l, c_i, c_p, c_p, c_i, c_i] + [c_p] * 7 + [c_i, c_p, c_p]),
     "papc_pg_planes_bytes": (ctypes.c_size_t, [c_l, c_l]),
     "papc_pg_prep_weights_f32": (c_i, [c_p, c_i, c_p]),
     "papc_pg_prep_rows_f32": (c_i, [c_p, c_p]),

@@ -4,6 +4,7 @@
 // Reference ops: nn.BatchNorm2D (train) + F.relu + paddle.max(axis=2),
 // /root/reference/PAPC/models/layers/pointnet2_basic_layers.py:190,217,219.
 #include "common.h"
+#include "finalize.h"
 
 namespace papc {
 
@@ -608,9 +609,8 @@ struct TransposeBatch {
     int ld[8], copy[8];      // source row stride; copy != 0: dst [rows, cols] = the block itself (a column slice made contiguous), not its transpose
 };
 
-__global__ __launch_bounds__(256) void transpose_batch_kernel(TransposeBatch t)
+__device__ __forceinline__ void transpose_batch_body(float (&tile)[32][33], const TransposeBatch &t)
 {
-    __shared__ float tile[32][33];
     const int m = blockIdx.y;
     const int rows = t.rows[m], cols = t.cols[m];
     const int tiles_c = (cols + 31) >> 5, tiles = ((rows + 31) >> 5) * tiles_c;
@@ -635,6 +635,22 @@ __global__ __launch_bounds__(256) void transpose_batch_kernel(TransposeBatch t)
         }
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(256) void transpose_batch_kernel(TransposeBatch t)
+{
+    __shared__ float tile[32][33];
+    transpose_batch_body(tile, t);
+}
+
+// ... with the coordinates-only first layer's forward finalize (finalize.h) as ONE extra workgroup, the first of row `count` of the grid:
+// both are weight-only work at the head of a training step, and a launch of one workgroup costs what the launch of 33 does
+__global__ __launch_bounds__(256) void transpose_batch_l1_kernel(TransposeBatch t, int count, XyzL1Fin a)
+{
+    __shared__ float tile[32][33];
+    __shared__ double lds[XYZ_L1_FIN_LDS];
+    if ((int)blockIdx.y < count) transpose_batch_body(tile, t);
+    else if (blockIdx.x == 0) xyz_l1_finalize_body(lds, a);
 }
 
 // papc_bn_finalize_f32 with `bytes` (a multiple of 16) of `clr` zeroed by the same launch (internal: sa_mlp.hip, the key buffer of the
@@ -854,6 +870,21 @@ int papc_transpose_batch_f32(const float *const *src, float *const *dst, const i
     return papc_transpose_batch_ld_f32(src, nullptr, dst, rows, cols, nullptr, count, stream);
 }
 
+// the launch arguments of `count` transposes; the widest job's tile count in *max_tiles
+static int fill_transposes(TransposeBatch &t, int *max_tiles, const float *const *src, const int *src_ld, float *const *dst, const int *rows, const int *cols,
+                           const int *copy, int count)
+{
+    *max_tiles = 1;
+    for (int i = 0; i < count; ++i) {
+        PAPC_REQUIRE(src[i] && dst[i] && rows[i] >= 1 && cols[i] >= 1, PAPC_E_INVALID, "papc_transpose_batch_f32: bad entry %d", i);
+        t.src[i] = src[i]; t.dst[i] = dst[i]; t.rows[i] = rows[i]; t.cols[i] = cols[i];
+        t.ld[i] = src_ld ? src_ld[i] : cols[i]; t.copy[i] = copy ? copy[i] : 0;
+        PAPC_REQUIRE(t.ld[i] >= cols[i], PAPC_E_INVALID, "papc_transpose_batch_f32: entry %d: row stride shorter than a row", i);
+        *max_tiles = std::max(*max_tiles, (int)(cdiv(rows[i], 32) * cdiv(cols[i], 32)));
+    }
+    return PAPC_OK;
+}
+
 int papc_transpose_batch_ld_f32(const float *const *src, const int *src_ld, float *const *dst, const int *rows, const int *cols, const int *copy, int count,
                                 papc_stream_t stream)
 {
@@ -861,18 +892,31 @@ int papc_transpose_batch_ld_f32(const float *const *src, const int *src_ld, floa
     PAPC_REQUIRE(count >= 1 && count <= 8, PAPC_E_INVALID, "papc_transpose_batch_f32: count=%d not in [1, 8]", count);
     TransposeBatch t{};
     int max_tiles = 1;
-    for (int i = 0; i < count; ++i) {
-        PAPC_REQUIRE(src[i] && dst[i] && rows[i] >= 1 && cols[i] >= 1, PAPC_E_INVALID, "papc_transpose_batch_f32: bad entry %d", i);
-        t.src[i] = src[i]; t.dst[i] = dst[i]; t.rows[i] = rows[i]; t.cols[i] = cols[i];
-        t.ld[i] = src_ld ? src_ld[i] : cols[i]; t.copy[i] = copy ? copy[i] : 0;
-        PAPC_REQUIRE(t.ld[i] >= cols[i], PAPC_E_INVALID, "papc_transpose_batch_f32: entry %d: row stride shorter than a row", i);
-        max_tiles = std::max(max_tiles, (int)(cdiv(rows[i], 32) * cdiv(cols[i], 32)));
-    }
+    const int rc = fill_transposes(t, &max_tiles, src, src_ld, dst, rows, cols, copy, count);
+    if (rc != PAPC_OK) return rc;
     hipStream_t st = as_stream(stream);
     ProfScope prof(PAPC_K_MISC, st);
     hipLaunchKernelGGL(transpose_batch_kernel, dim3((unsigned)std::min(max_tiles, 512), (unsigned)count), dim3(256), 0, st, t);
     return check_launch("papc_transpose_batch_f32");
 }
+
+}  // extern "C"
+
+// (internal: sa_mlp.hip, papc_sa_mlp_xyz1_prep) `count` in [0, 8] transposes and the first layer's finalize in one launch
+int papc::transpose_batch_l1(const float *const *src, const int *src_ld, float *const *dst, const int *rows, const int *cols, const int *copy, int count,
+                             const XyzL1Fin &a, hipStream_t st)
+{
+    PAPC_REQUIRE(count >= 0 && count <= 8 && (count == 0 || (src && dst && rows && cols)), PAPC_E_INVALID, "transpose_batch_l1: bad arguments");
+    TransposeBatch t{};
+    int max_tiles = 1;
+    const int rc = fill_transposes(t, &max_tiles, src, src_ld, dst, rows, cols, copy, count);
+    if (rc != PAPC_OK) return rc;
+    ProfScope prof(PAPC_K_MISC, st);
+    hipLaunchKernelGGL(transpose_batch_l1_kernel, dim3((unsigned)std::min(max_tiles, 512), (unsigned)count + 1), dim3(256), 0, st, t, count, a);
+    return check_launch("papc_sa_mlp_xyz1_prep");
+}
+
+extern "C" {
 
 static int adam_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr, double beta1, double beta2, float eps,
                      float weight_decay, int step, float grad_scale, bool zero, papc_stream_t stream, const char *who)

@@ -73,6 +73,8 @@ static const KnobDef g_knob_defs[KNOB_COUNT] = {
     {"PAPC_PG_GROUP", 1, 0, 1},            // papc_pg_gemm_group_f32: a layer's dX and dW products in one grid (0: one launch per product)
     {"PAPC_PG_PIPE", 1, 0, 1},             // pg_gemm_kernel / pg_gemm_group_kernel: 1 = four-slot k16 LDS ring, DMA in flight across the barriers (0, and with PAPC_PG_DBG or PAPC_PG_NS=3: the k32 stage loop); measured in DESIGN 3.8
     {"PAPC_SEG_EPI", 1, 0, 1},             // papc_sa_mlp_fwd, compacted pooled stack: the last layer's forward keeps the ragged groups' extrema (atomic-max keys) and a select kernel replaces seg_max_kernel's pass over y (0: that pass); bit-identical either way
+    {"PAPC_FOLD_FIN", 1, 0, 1},            // a backward with a fold list: the max layer's float64 fold joins the deferred folds and its closed form, with the coordinates-only layer's, runs in ONE finalize launch behind them (0: their three launches inside the backward); bit-identical either way
+    {"PAPC_XYZ1_RIDE", 1, 0, 1},           // papc_sa_mlp_xyz1_prep: the coordinates-only first layer's finalize as one extra workgroup of the step's weight transposes (0: a launch of its own behind them); bit-identical either way
 };
 static int g_knobs[KNOB_COUNT];
 static int knob_parse(int id, const char *e)
@@ -164,6 +166,7 @@ int64_t papc_abi_sizeof(const char *struct_name)
     PAPC_SIZEOF(papc_reduce_job)
     PAPC_SIZEOF(papc_fold_job)
     PAPC_SIZEOF(papc_fold_list)
+    PAPC_SIZEOF(papc_fold_fin)
     PAPC_SIZEOF(papc_sa_desc)
     PAPC_SIZEOF(papc_sa_layer)
     PAPC_SIZEOF(papc_compact_src)

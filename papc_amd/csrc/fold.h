@@ -29,11 +29,34 @@
 // SLICE TREE  reduce_partials_strided_kernel (folds.hip), its only user: 64 slices, slice sl sums chunks sl, sl + 64, ... to 0.f in
 //   order (a missing chunk adds 0.f), then red[sl] += red[sl + h] for h = 32, 16, ... 1.
 //
+// QUARTER FOLD  fold_quarters_f64: a wave owns 16 elements; lane & 15 = element, lane >> 4 = quarter q of the chunks,
+//   [q * per, min(n_chunks, (q + 1) * per)) with per = ceil(n_chunks / 4).  In float64:
+//     s_q = 0.0;  s_q += part[t] for the quarter's t in order;      total = ((s_0 + s_1) + s_2) + s_3
+//   (eight loads in flight, the sum does not depend on it)
+//     dw_max_fold_kernel (mlp_dw.hip) and fold_jobs_kernel's PAPC_FOLD_F64Q kind (folds.hip): a deferred fold has that launch's bits
+//
 // What a fold does with its total is the caller's: `accumulate` adds it to what the output held, as the last add.
 #pragma once
 #include "common.h"
 
 namespace papc {
+
+// ---- host: the entries of a papc_fold_list beyond the float fold (include/papc_hip.h) -----------------------------------------------------
+static inline bool fold_list_room(const papc_fold_list *fl, int slots) { return fl && fl->jobs && fl->count + slots <= fl->capacity; }
+static inline void fold_list_push_f64q(papc_fold_list *fl, const float *partial, int n_chunks, int64_t ld, int n, double *out)
+{
+    papc_fold_job &j = fl->jobs[fl->count++];
+    memset(&j, 0, sizeof(j));
+    j.partial = partial; j.n_chunks = n_chunks; j.ld = ld; j.rows = PAPC_FOLD_F64Q; j.cols = n; j.out = reinterpret_cast<float *>(out); j.out_ld = n;
+}
+static inline void fold_list_push_fin(papc_fold_list *fl, const papc_fold_fin &f)
+{
+    papc_fold_job &j = fl->jobs[fl->count];
+    memset(&j, 0, sizeof(j) * (1 + PAPC_FOLD_FIN_SLOTS));
+    j.rows = PAPC_FOLD_FIN; j.n_chunks = PAPC_FOLD_FIN_SLOTS; j.cols = f.kind;
+    memcpy(&fl->jobs[fl->count + 1], &f, sizeof(f));
+    fl->count += 1 + PAPC_FOLD_FIN_SLOTS;
+}
 
 template <typename V> __device__ __forceinline__ V fold_zero();
 template <> __device__ __forceinline__ float fold_zero<float>() { return 0.f; }
@@ -90,6 +113,29 @@ __device__ __forceinline__ V fold_in_order(const float *__restrict__ part, int64
             if (t0 + j < n_chunks) { if (START == FOLD_FROM_FIRST && t0 + j == 0) s = v[j]; else s = fold_add(s, v[j]); }
     }
     return s;
+}
+
+// The quarter fold of element e (every lane of a wave calls; `live` = this lane's element exists).  True on the one lane per element that
+// holds the total.
+__device__ __forceinline__ bool fold_quarters_f64(const float *__restrict__ part, int64_t ld, int n_chunks, int64_t e, bool live, double &total)
+{
+    const int l = threadIdx.x & 15, q = (threadIdx.x & 63) >> 4;
+    const int per = (n_chunks + 3) / 4, c0 = q * per, c1 = min(n_chunks, c0 + per);
+    double s = 0.0;
+    if (live) {
+        int c = c0;
+        for (; c + 8 <= c1; c += 8) {
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = part[(int64_t)(c + j) * ld + e];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s += (double)v[j];
+        }
+        for (; c < c1; ++c) s += (double)part[(int64_t)c * ld + e];
+    }
+    const double s1 = __shfl(s, l + 16), s2 = __shfl(s, l + 32), s3 = __shfl(s, l + 48);
+    total = ((s + s1) + s2) + s3;
+    return q == 0 && live;
 }
 
 }  // namespace papc

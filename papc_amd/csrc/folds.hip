@@ -1,6 +1,9 @@
 // folds.hip -- the generic folds of per-chunk partial sums (gfx950): out[i] (+)= sum_t partial[t, i] in a FIXED order, so that a training
 // step is bit-reproducible.  The orders are specified in fold.h and nowhere else.  The folds that belong to one producer (pg_fold_kernel,
 // ct_fold_kernel, cc_fold_kernel, the pfn tail, ...) live beside it and call into fold.h as well.
+#include <vector>
+
+#include "finalize.h"
 #include "fold.h"
 
 namespace papc {
@@ -94,11 +97,13 @@ __global__ __launch_bounds__(1024) void reduce_partials_strided_kernel(const flo
 //   many chunks, float4:  the lane fold of 64 float4 (n % 4 == 0, contiguous output): 1 KB per wave and chunk;
 //   few chunks (wide):    the in-order fold from the first chunk, a thread owns a float4 of 4 * 64 * FW consecutive elements per workgroup:
 //                         the split-K partials of the planes path (<= 8 chunks of up to 512 K elements).
+// and one more kind: the float64 quarter fold (PAPC_FOLD_F64Q), 16 elements per wave -- the no-store max layer's dW sums, which its
+// closed form reads in the finalize launch below.
 struct FoldBatch {
     const float *part[PAPC_FOLD_MAX]; float *out[PAPC_FOLD_MAX];
     int64_t ld[PAPC_FOLD_MAX], out_ld[PAPC_FOLD_MAX];
     int n_chunks[PAPC_FOLD_MAX], rows[PAPC_FOLD_MAX], cols[PAPC_FOLD_MAX], wg0[PAPC_FOLD_MAX + 1];
-    unsigned acc_mask, wide_mask, vec_mask;
+    unsigned acc_mask, wide_mask, vec_mask, f64_mask;
     int count;
 };
 // FW = chunk lanes (waves) per workgroup (PAPC_FOLD_WAVES).  Round 6 tried 8 instead of 16 -- the step's 654 workgroups of 1024 threads are two
@@ -117,7 +122,13 @@ __global__ __launch_bounds__(64 * FW) void fold_jobs_kernel(FoldBatch b)
     const int n_chunks = b.n_chunks[job], cols = b.cols[job];
     const int64_t n = (int64_t)b.rows[job] * cols;
     const bool acc = (b.acc_mask >> job) & 1u;
-    if ((b.wide_mask >> job) & 1u) {        // few chunks, contiguous output (out_ld == cols), n % 4 == 0, 16-byte aligned
+    if ((b.f64_mask >> job) & 1u) {         // PAPC_FOLD_F64Q: the quarter fold into a double output, a wave owns 16 elements
+        const int64_t e = ((int64_t)wg * FW + (threadIdx.x >> 6)) * 16 + (threadIdx.x & 15);
+        double t;
+        if (fold_quarters_f64(part, ld, n_chunks, e, e < n, t)) reinterpret_cast<double *>(out)[e] = t;
+        return;
+    }
+    if ((b.wide_mask >> job) & 1u) {       // few chunks, contiguous output (out_ld == cols), n % 4 == 0, 16-byte aligned
         const int64_t e = ((int64_t)wg * (64 * FW) + threadIdx.x) * 4;
         if (e >= n) return;
         float4 s = fold_in_order<8, FOLD_FROM_FIRST, float4>(part, ld, n_chunks, e);
@@ -147,10 +158,56 @@ __global__ __launch_bounds__(64 * FW) void fold_jobs_kernel(FoldBatch b)
     }
 }
 
+// ---- deferred finalizes: the closed forms (finalize.h) that nothing inside the backward waits for, in ONE launch behind the folds ---------
+// Flat grid as above: workgroup b belongs to the record whose [wg0, wg0 + nwg) range holds it; 1024 threads, four output rows / channels each.
+constexpr int FIN_MAX = 4;
+struct FinBatch { papc_fold_fin f[FIN_MAX]; int wg0[FIN_MAX + 1], count; };
+__global__ __launch_bounds__(1024) void fold_fin_kernel(FinBatch b)
+{
+    __shared__ double lds[DWMAX_FIN_LDS > XYZ_BWD_FIN_LDS ? DWMAX_FIN_LDS : XYZ_BWD_FIN_LDS];
+    int r = 0;
+    while (r + 1 < b.count && (int)blockIdx.x >= b.wg0[r + 1]) ++r;
+    const int wg = (int)blockIdx.x - b.wg0[r];
+    const papc_fold_fin &f = b.f[r];
+    if (f.kind == PAPC_FIN_DW_MAX)
+        dw_max_finalize_body(lds, wg, 1024, static_cast<const double *>(f.src), f.w, f.e, f.scale, f.c1, f.inv_m, f.C, f.dw, f.accumulate);
+    else
+        xyz_l1_bwd_finalize_body(lds, wg, static_cast<const float *>(f.src), f.parts, f.M, f.C, f.gram, f.w, f.ldw, f.xcol0, f.bias, f.mean, f.invstd,
+                                 f.scale, f.dgamma, f.dbeta, f.dw, f.accumulate);
+}
+
 }  // namespace papc
 
 
 using namespace papc;
+
+static int launch_fins(const papc_fold_fin *fins, int count, hipStream_t st)
+{
+    // the records of one launch run concurrently and end in a read-modify-write of dw (dgamma, dbeta): a record that writes where an earlier one of
+    // the launch does (a module applied twice in one backward pass) starts the next launch, so such records apply in list order
+    for (int r0 = 0; r0 < count;) {
+        FinBatch b;
+        memset(&b, 0, sizeof(b));
+        int n = 0, wgs = 0;
+        for (; n < FIN_MAX && r0 + n < count; ++n) {
+            const papc_fold_fin &f = fins[r0 + n];
+            bool shared = false;
+            for (int k = 0; k < n && !shared; ++k) shared = b.f[k].dw == f.dw || (f.dgamma && b.f[k].dgamma == f.dgamma) || (f.dbeta && b.f[k].dbeta == f.dbeta);
+            if (shared) break;
+            b.f[n] = f;
+            b.wg0[n] = wgs;
+            wgs += (int)cdiv(f.C, 4);
+        }
+        b.wg0[n] = wgs;
+        b.count = n;
+        ProfScope prof(PAPC_K_BWD_DW, st);
+        hipLaunchKernelGGL(fold_fin_kernel, dim3((unsigned)wgs), dim3(1024), 0, st, b);
+        const int rc = check_launch("papc_fold_jobs_f32 (finalizes)");
+        if (rc != PAPC_OK) return rc;
+        r0 += n;
+    }
+    return PAPC_OK;
+}
 
 // Two fold jobs whose output RANGES intersect can still write disjoint elements: column blocks of one row-major matrix (the same row stride:
 // the xyz and the feature columns of the gather-add first layer's dW).  True only where that is certain.
@@ -205,11 +262,26 @@ int papc_reduce_partials_batch_f32(const papc_reduce_job *jobs, int count, papc_
     return check_launch("papc_reduce_partials_batch_f32");
 }
 
-int papc_fold_jobs_f32(const papc_fold_job *jobs, int count, papc_stream_t stream)
+int papc_fold_jobs_f32(const papc_fold_job *list, int list_count, papc_stream_t stream)
 {
-    PAPC_REQUIRE(jobs, PAPC_E_INVALID, "papc_fold_jobs_f32: null jobs");
-    PAPC_REQUIRE(count >= 1, PAPC_E_INVALID, "papc_fold_jobs_f32: count=%d", count);
+    PAPC_REQUIRE(list, PAPC_E_INVALID, "papc_fold_jobs_f32: null jobs");
+    PAPC_REQUIRE(list_count >= 1, PAPC_E_INVALID, "papc_fold_jobs_f32: count=%d", list_count);
     hipStream_t st = as_stream(stream);
+    // the finalize records (a header slot + the record's bytes in the slots behind it) leave the list: they run behind every fold
+    std::vector<papc_fold_job> folds;
+    std::vector<papc_fold_fin> fins;
+    for (int i = 0; i < list_count; ++i) {
+        if (list[i].rows != PAPC_FOLD_FIN) { folds.push_back(list[i]); continue; }
+        PAPC_REQUIRE(list[i].n_chunks == PAPC_FOLD_FIN_SLOTS && i + PAPC_FOLD_FIN_SLOTS < list_count, PAPC_E_INVALID, "papc_fold_jobs_f32: truncated finalize record at job %d", i);
+        papc_fold_fin f;
+        memcpy(&f, &list[i + 1], sizeof(f));
+        PAPC_REQUIRE((f.kind == PAPC_FIN_DW_MAX || f.kind == PAPC_FIN_XYZ_BWD) && f.kind == list[i].cols && f.C >= 1 && f.src && f.dw, PAPC_E_INVALID,
+                     "papc_fold_jobs_f32: bad finalize record at job %d", i);
+        fins.push_back(f);
+        i += PAPC_FOLD_FIN_SLOTS;
+    }
+    const papc_fold_job *jobs = folds.data();
+    const int count = (int)folds.size();
     const int FW = knob(KNOB_FOLD_WAVES) == 16 ? 16 : 8;
     // The jobs of ONE launch run concurrently (a flat grid), and a job ends in a read-modify-write of its output: a launch holds only jobs
     // whose output ranges [out, out + (rows - 1) * out_ld + cols) are pairwise disjoint.  A job that overlaps one of the current launch
@@ -223,25 +295,29 @@ int papc_fold_jobs_f32(const papc_fold_job *jobs, int count, papc_stream_t strea
         int nj = 0;
         for (; nj < PAPC_FOLD_MAX && j0 + nj < count; ++nj) {
             const int i = nj;
-            const papc_fold_job &j = jobs[j0 + i];
+            papc_fold_job j = jobs[j0 + i];
+            const bool f64 = j.rows == PAPC_FOLD_F64Q;       // one row of cols doubles
+            if (f64) j.rows = 1;
             PAPC_REQUIRE(j.partial && j.out, PAPC_E_INVALID, "papc_fold_jobs_f32: null pointer in job %d", j0 + i);
             PAPC_REQUIRE(j.n_chunks >= 1 && j.rows >= 1 && j.cols >= 1 && j.ld >= (int64_t)j.rows * j.cols && j.out_ld >= j.cols, PAPC_E_INVALID,
                          "papc_fold_jobs_f32: bad sizes in job %d", j0 + i);
+            PAPC_REQUIRE(!f64 || (!j.accumulate && ((uintptr_t)j.out & 7) == 0), PAPC_E_INVALID, "papc_fold_jobs_f32: bad float64 job %d", j0 + i);
             lo[i] = (uintptr_t)j.out;
-            hi[i] = lo[i] + sizeof(float) * (uintptr_t)((int64_t)(j.rows - 1) * j.out_ld + j.cols);
+            hi[i] = lo[i] + (f64 ? sizeof(double) : sizeof(float)) * (uintptr_t)((int64_t)(j.rows - 1) * j.out_ld + j.cols);
             bool overlaps = false;
             for (int k = 0; k < i && !overlaps; ++k)
                 overlaps = lo[i] < hi[k] && lo[k] < hi[i] && !disjoint_column_blocks(jobs[j0 + k], j);
             if (overlaps) break;                // (i >= 1 here: the launch below is never empty)
             const int64_t n = (int64_t)j.rows * j.cols;
-            const bool wide = j.n_chunks <= 16 && n >= 16384 && n % 4 == 0 && j.ld % 4 == 0 && (j.rows == 1 || j.out_ld == j.cols) && aligned16(j.partial) && aligned16(j.out);
+            const bool wide = !f64 && j.n_chunks <= 16 && n >= 16384 && n % 4 == 0 && j.ld % 4 == 0 && (j.rows == 1 || j.out_ld == j.cols) && aligned16(j.partial) && aligned16(j.out);
             b.part[i] = j.partial; b.out[i] = j.out; b.ld[i] = j.ld; b.out_ld[i] = j.out_ld; b.n_chunks[i] = j.n_chunks; b.rows[i] = j.rows; b.cols[i] = j.cols;
             if (j.accumulate) b.acc_mask |= 1u << i;
-            const bool vec = !wide && n >= 1024 && n % 4 == 0 && j.ld % 4 == 0 && (j.rows == 1 || j.out_ld == j.cols) && aligned16(j.partial) && aligned16(j.out);
+            const bool vec = !f64 && !wide && n >= 1024 && n % 4 == 0 && j.ld % 4 == 0 && (j.rows == 1 || j.out_ld == j.cols) && aligned16(j.partial) && aligned16(j.out);
             if (wide) b.wide_mask |= 1u << i;
             if (vec) b.vec_mask |= 1u << i;
+            if (f64) b.f64_mask |= 1u << i;
             b.wg0[i] = (int)wgs;
-            wgs += wide ? cdiv(n, 4 * 64 * FW) : (vec ? cdiv(n, 256) : cdiv(n, 64));
+            wgs += f64 ? cdiv(n, 16 * FW) : wide ? cdiv(n, 4 * 64 * FW) : (vec ? cdiv(n, 256) : cdiv(n, 64));
             PAPC_REQUIRE(wgs < (1ll << 30), PAPC_E_UNSUPPORTED, "papc_fold_jobs_f32: too many elements");
         }
         b.wg0[nj] = (int)wgs;
@@ -253,7 +329,7 @@ int papc_fold_jobs_f32(const papc_fold_job *jobs, int count, papc_stream_t strea
         if (rc != PAPC_OK) return rc;
         j0 += nj;
     }
-    return PAPC_OK;
+    return fins.empty() ? PAPC_OK : launch_fins(fins.data(), (int)fins.size(), st);
 }
 
 int papc_reduce_partials_f32(const float *partial, int n_chunks, int64_t n, float *out, int accumulate, papc_stream_t stream)

@@ -15,6 +15,8 @@
 // idx -> address -> data dependency never sits in front of the matrix pipe.
 #include <type_traits>
 #include "mlp_loaders.h"
+#include "finalize.h"
+#include "fold.h"
 
 namespace papc {
 
@@ -1256,51 +1258,23 @@ __global__ __launch_bounds__(512, 2) void dw_rows_max_kernel(DwMaxArgs p)
     }
 }
 
-// chunk partials -> double sums: one wave per 16 elements, four quarter-ranges of the chunks in parallel (loads unrolled: a serial chain of
-// 128 L2 round trips otherwise), quarters added in fixed order.  No LDS and one wave, so that the launch finds room beside another
-// stream's persistent GEMM (config 3: the 256-thread form waited 135 us on average for a CU to drain)
+// chunk partials -> double sums: one wave per 16 elements, the quarter fold of fold.h (loads unrolled: a serial chain of 128 L2 round trips
+// otherwise).  No LDS and one wave, so that the launch finds room beside another stream's persistent GEMM (config 3: the 256-thread form
+// waited 135 us on average for a CU to drain)
 __global__ __launch_bounds__(64) void dw_max_fold_kernel(const float *__restrict__ partial, int n_chunks, int64_t part_ld, int n, double *__restrict__ out)
 {
-    const int l = threadIdx.x & 15, q = threadIdx.x >> 4;
-    const int e = blockIdx.x * 16 + l;
-    const int per = (n_chunks + 3) / 4, c0 = q * per, c1 = min(n_chunks, c0 + per);
-    double s = 0.0;
-    if (e < n) {
-        int c = c0;
-        for (; c + 8 <= c1; c += 8) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = partial[(int64_t)(c + j) * part_ld + e];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) s += (double)v[j];
-        }
-        for (; c < c1; ++c) s += (double)partial[(int64_t)c * part_ld + e];
-    }
-    const double s1 = __shfl(s, l + 16), s2 = __shfl(s, l + 32), s3 = __shfl(s, l + 48);
-    if (q == 0 && e < n) out[e] = ((s + s1) + s2) + s3;
+    const int e = blockIdx.x * 16 + (threadIdx.x & 15);
+    double t;
+    if (fold_quarters_f64(partial, part_ld, n_chunks, e, e < n, t)) out[e] = t;
 }
 
-// dW[c, i] = T[c, i] - sc_c c1_c S_i - e_c sum_j W[c, j] (G[j, i] - S_j S_i / M); four rows of dW per workgroup
+// the closed form of finalize.h as a launch of its own: four rows of dW per workgroup
 __global__ __launch_bounds__(256) void dw_max_finalize_kernel(const double *__restrict__ fold, const float *__restrict__ w, const float *__restrict__ e,
                                                               const float *__restrict__ scale, const float *__restrict__ c1, double inv_m, int Cout,
                                                               float *__restrict__ dw, int accumulate)
 {
-    constexpr int CI = 64;
-    __shared__ double gc[CI][CI];
-    const int tid = threadIdx.x;
-    const double *G = fold + (int64_t)Cout * CI, *S = G + CI * CI;
-    for (int q = tid; q < CI * CI; q += 256) {
-        const int j = q >> 6, i = q & 63;
-        gc[j][i] = G[q] - S[j] * S[i] * inv_m;
-    }
-    __syncthreads();
-    const int i = tid & 63, c = 4 * blockIdx.x + (tid >> 6);
-    if (c >= Cout) return;
-    double dot = 0.0;
-    for (int j = 0; j < CI; ++j) dot += (double)w[(int64_t)c * CI + j] * gc[j][i];
-    const double v = fold[(int64_t)c * CI + i] - (double)scale[c] * (double)c1[c] * S[i] - (double)e[c] * dot;
-    float *o = dw + (int64_t)c * CI + i;
-    *o = accumulate ? *o + (float)v : (float)v;
+    __shared__ double gc[DWMAX_FIN_LDS];
+    dw_max_finalize_body(gc, blockIdx.x, 256, fold, w, e, scale, c1, inv_m, Cout, dw, accumulate);
 }
 
 static void dw_dbg_report(const DwArgs &p, int xm, int dm)
@@ -1527,6 +1501,13 @@ extern "C" int papc_mlp_bwd_dw_max_f32(const float *psel, const int32_t *argmax,
                                        const float *w, const float *e, const float *scale, const float *c1, int64_t M, int Cin, int Cout,
                                        float *workspace, float *dw, int accumulate, papc_stream_t stream)
 {
+    return papc_mlp_bwd_dw_max_defer_f32(psel, argmax, K, x, bn_scale, bn_shift, w, e, scale, c1, M, Cin, Cout, workspace, dw, accumulate, nullptr, stream);
+}
+
+extern "C" int papc_mlp_bwd_dw_max_defer_f32(const float *psel, const int32_t *argmax, int K, const float *x, const float *bn_scale, const float *bn_shift,
+                                             const float *w, const float *e, const float *scale, const float *c1, int64_t M, int Cin, int Cout,
+                                             float *workspace, float *dw, int accumulate, papc_fold_list *defer, papc_stream_t stream)
+{
     PAPC_REQUIRE(psel && argmax && x && bn_scale && bn_shift && w && e && scale && c1 && workspace && dw, PAPC_E_INVALID, "papc_mlp_bwd_dw_max_f32: null pointer");
     PAPC_REQUIRE(papc_mlp_max_nostore_ok(M, Cin, Cout, K), PAPC_E_UNSUPPORTED,
                  "papc_mlp_bwd_dw_max_f32: not built for M=%lld Cin=%d Cout=%d K=%d (see papc_mlp_max_nostore_ok)", (long long)M, Cin, Cout, K);
@@ -1541,6 +1522,16 @@ extern "C" int papc_mlp_bwd_dw_max_f32(const float *psel, const int32_t *argmax,
     hipStream_t st = as_stream(stream);
     ProfScope prof(PAPC_K_BWD_DW, st);
     hipLaunchKernelGGL(dw_rows_max_kernel, dim3((unsigned)(2 * p.n_chunks)), dim3(512), 0, st, p);
+    if (knob(KNOB_FOLD_FIN) && fold_list_room(defer, 2 + PAPC_FOLD_FIN_SLOTS)) {
+        // nothing downstream in the backward reads dW: the fold joins the step's deferred folds, the closed form its finalize launch
+        fold_list_push_f64q(defer, workspace, p.n_chunks, (int64_t)n, n, fold);
+        papc_fold_fin f;
+        memset(&f, 0, sizeof(f));
+        f.kind = PAPC_FIN_DW_MAX; f.accumulate = accumulate; f.C = Cout; f.inv_m = 1.0 / (double)M;
+        f.src = fold; f.w = w; f.e = e; f.scale = scale; f.c1 = c1; f.dw = dw;
+        fold_list_push_fin(defer, f);
+        return check_launch("papc_mlp_bwd_dw_max_f32");
+    }
     hipLaunchKernelGGL(dw_max_fold_kernel, dim3((unsigned)cdiv(n, 16)), dim3(64), 0, st, workspace, p.n_chunks, (int64_t)n, n, fold);
     hipLaunchKernelGGL(dw_max_finalize_kernel, dim3((unsigned)cdiv(Cout, 4)), dim3(256), 0, st, fold, w, e, scale, c1, 1.0 / (double)M, Cout, dw, accumulate);
     return check_launch("papc_mlp_bwd_dw_max_f32");

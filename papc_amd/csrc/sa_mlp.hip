@@ -14,6 +14,7 @@
 //
 // All buffers are caller-owned device memory; nothing is allocated, nothing synchronises, every launch goes to the given stream.
 #include "common.h"
+#include "finalize.h"
 
 #define SA_CALL(expr)                 \
     do {                              \
@@ -540,6 +541,33 @@ int papc_sa_mlp_plan(const papc_sa_desc *desc, const papc_sa_io *io, papc_sa_pla
     return PAPC_OK;
 }
 
+int papc_sa_mlp_xyz1_prep(const papc_sa_plan *plan, const papc_sa_io *io, const float *const *src, const int *src_ld, float *const *dst, const int *rows,
+                          const int *cols, const int *copy, int count, papc_stream_t st)
+{
+    PAPC_REQUIRE(plan && io && io->saved, PAPC_E_INVALID, "papc_sa_mlp_xyz1_prep: null pointer");
+    const papc_sa_plan &p = *plan;
+    const papc_sa_desc &d = p.d;
+    PAPC_REQUIRE(p.xyz1 && !p.planes && io->xc && io->xc_gram, PAPC_E_UNSUPPORTED,
+                 "papc_sa_mlp_xyz1_prep: needs a plan with the coordinates-only first layer and the pregrouped coordinates (xc, xc_gram)");
+    PAPC_REQUIRE(count >= 0 && count <= 8, PAPC_E_INVALID, "papc_sa_mlp_xyz1_prep: count=%d not in [0, 8]", count);
+    const papc_sa_layer &ly = io->layer[0];
+    PAPC_REQUIRE(ly.w && ly.gamma && ly.beta, PAPC_E_INVALID, "papc_sa_mlp_xyz1_prep: layer 0 lacks w / gamma / beta");
+    SavedPtrs s;
+    layout_saved(p, io->saved, s);
+    const int cout = d.cout[0];
+    float *cst = s.cst[0];
+    if (!knob(KNOB_XYZ1_RIDE)) {      // the two launches the ride replaces, in their order
+        if (count) SA_CALL(papc_transpose_batch_ld_f32(src, src_ld, dst, rows, cols, copy, count, st));
+        return papc_xyz_l1_finalize_f32(io->xc_gram, 1, rows_of(d), ly.w, p.cin0, 0, ly.b, ly.gamma, ly.beta, d.eps, d.momentum, cout, cst, cst + cout,
+                                        cst + 2 * cout, cst + 3 * cout, ly.running_mean, ly.running_var, s.wf, s.gram, st);
+    }
+    XyzL1Fin a;
+    a.partial = io->xc_gram; a.parts = 1; a.M = (double)rows_of(d); a.w = ly.w; a.ldw = p.cin0; a.xcol0 = 0; a.bias = ly.b; a.gamma = ly.gamma; a.beta = ly.beta;
+    a.eps = d.eps; a.momentum = d.momentum; a.C = cout; a.mean = cst; a.invstd = cst + cout; a.scale = cst + 2 * cout; a.shift = cst + 3 * cout;
+    a.rmean = ly.running_mean; a.rvar = ly.running_var; a.wf = s.wf; a.gram = s.gram;
+    return transpose_batch_l1(src, src_ld, dst, rows, cols, copy, count, a, as_stream(st));
+}
+
 int papc_sa_mlp_fwd(const papc_sa_plan *plan, const papc_sa_io *io, papc_stream_t st)
 {
     PAPC_REQUIRE(plan && io && io->out && io->saved && io->scratch, PAPC_E_INVALID, "papc_sa_mlp_fwd: null pointer");
@@ -559,6 +587,8 @@ int papc_sa_mlp_fwd(const papc_sa_plan *plan, const papc_sa_io *io, papc_stream_
     SavedPtrs s; FwdPtrs f;
     layout_saved(p, io->saved, s);
     layout_fwd(p, io->scratch, f);
+    PAPC_REQUIRE(!(d.disable & PAPC_SA_L1_DONE) || (p.xyz1 && io->xc && io->xc_gram), PAPC_E_INVALID,
+                 "papc_sa_mlp_fwd: PAPC_SA_L1_DONE without the path papc_sa_mlp_xyz1_prep serves");
     const int parts = papc_mlp_gemm_parts(M);
     // compacted stack: the producers weigh their statistics with the rows' multiplicities themselves (papc_mlp_gemm_rows_w_f32, papc_group_src.wstat);
     // PAPC_SA_NO_WSTATS: unweighted sums + one papc_bn_stats_corr_f32 launch per layer
@@ -605,8 +635,10 @@ int papc_sa_mlp_fwd(const papc_sa_plan *plan, const papc_sa_io *io, papc_stream_
                 SA_CALL(papc_xyz_gram_fold_f32(f.gpart + 16, papc_xyz_parts(M), f.gpart, st));
                 xc = s.xc; gpart1 = f.gpart;
             }
-            SA_CALL(papc_xyz_l1_finalize_f32(gpart1, 1, M, ly.w, cin, 0, ly.b, ly.gamma, ly.beta, d.eps, d.momentum, cout, cst, cst + cout, cst + 2 * cout,
-                                             cst + 3 * cout, ly.running_mean, ly.running_var, s.wf, s.gram, st));
+            // (PAPC_SA_L1_DONE: papc_sa_mlp_xyz1_prep has written the constants into `saved` already, with the step's weight transposes)
+            if (!(d.disable & PAPC_SA_L1_DONE))
+                SA_CALL(papc_xyz_l1_finalize_f32(gpart1, 1, M, ly.w, cin, 0, ly.b, ly.gamma, ly.beta, d.eps, d.momentum, cout, cst, cst + cout, cst + 2 * cout,
+                                                 cst + 3 * cout, ly.running_mean, ly.running_var, s.wf, s.gram, st));
             prev_y = nullptr; prev_sc = cst + 2 * cout; prev_sh = cst + 3 * cout;
             cin = cout;
             continue;
@@ -744,8 +776,9 @@ int papc_sa_mlp_bwd(const papc_sa_plan *plan, const papc_sa_io *io, const papc_s
             int nbp = papc_xyz_bwd_parts(M);
             if (xyz_fused) nbp = papc_mlp_gemm_parts(M);      // (the partial sums came out of the layer above's dX kernel)
             else SA_CALL(papc_xyz_l1_bwd_f32(dz, xc, s.wf, M, cout, b.bpart, st));
-            SA_CALL(papc_xyz_l1_bwd_finalize_f32(b.bpart, nbp, M, cout, s.gram, ly.w, cin, 0, ly.b, cst, cst + cout, cst + 2 * cout, dgamma, dbeta, gr->dw[l],
-                                                 acc_w ? 1 : 0, st));
+            // (nothing waits for it: with a fold list it runs in the step's finalize launch, behind the deferred folds)
+            SA_CALL(papc_xyz_l1_bwd_finalize_defer_f32(b.bpart, nbp, M, cout, s.gram, ly.w, cin, 0, ly.b, cst, cst + cout, cst + 2 * cout, dgamma, dbeta, gr->dw[l],
+                                                       acc_w ? 1 : 0, gr->defer, st));
             if (gr->db[l] && !acc_w) SA_CALL(papc_fill_f32(gr->db[l], cout, 0.f, st));
             break;
         }
@@ -815,8 +848,8 @@ int papc_sa_mlp_bwd(const papc_sa_plan *plan, const papc_sa_io *io, const papc_s
         // ---- dW, db
         if (p.nostore && l == L - 1) {
             const float *pc = s.cst[l - 1];
-            SA_CALL(papc_mlp_bwd_dw_max_f32(b.psel, s.argmax, d.K, s.y[l - 1], pc + 2 * cin, pc + 3 * cin, ly.w, b.eq, cst + 2 * cout, c12, M, cin, cout, b.dwmax_ws,
-                                            gr->dw[l], acc_w ? 1 : 0, st));
+            SA_CALL(papc_mlp_bwd_dw_max_defer_f32(b.psel, s.argmax, d.K, s.y[l - 1], pc + 2 * cin, pc + 3 * cin, ly.w, b.eq, cst + 2 * cout, c12, M, cin, cout, b.dwmax_ws,
+                                                  gr->dw[l], acc_w ? 1 : 0, gr->defer, st));
             if (gr->db[l] && !acc_w) SA_CALL(papc_fill_f32(gr->db[l], cout, 0.f, st));
         } else {
             const int am = l == 0 ? (plain ? A_PLAIN_ : A_GROUP_) : (x1 ? A_XYZ_ : A_BNRELU_);

@@ -18,6 +18,8 @@
 // Sx / Sxx are accumulated in float64 (products of two fp32 values are exact there): the variance is a difference of second moments.
 // The grouped, centred coordinates themselves are written once per step as float4 rows xc [M, 4] (8 MB) that the consumers stream.
 #include "mlp_loaders.h"
+#include "finalize.h"
+#include "fold.h"
 
 namespace papc {
 
@@ -84,48 +86,11 @@ __global__ __launch_bounds__(256) void xyz_gram_fold_kernel(const double *__rest
     }
 }
 
-// moments [parts][16] -> gram[16] (fixed order), then per channel the BatchNorm constants and the folded first layer
-__global__ __launch_bounds__(256) void xyz_l1_finalize_kernel(const double *__restrict__ partial, int parts, double M, const float *__restrict__ w, int ldw,
-                                                              int xcol0, const float *__restrict__ bias, const float *__restrict__ gamma,
-                                                              const float *__restrict__ beta, float eps, float momentum, int C, float *mean,
-                                                              float *invstd, float *scale, float *shift, float *rmean, float *rvar, float *wf,
-                                                              double *gram)
+// moments -> gram [16], the BatchNorm constants and the folded first layer: the body of finalize.h as a launch of its own
+__global__ __launch_bounds__(256) void xyz_l1_finalize_kernel(XyzL1Fin a)
 {
-    __shared__ double red[16][16];
-    __shared__ double G[10];
-    const int e = threadIdx.x & 15, sl = threadIdx.x >> 4;      // 16 entries (10 used) x 16 slices
-    double s = 0.0;
-    if (e < 10) for (int t = sl; t < parts; t += 16) s += partial[(int64_t)t * 16 + e];
-    red[sl][e] = s;
-    __syncthreads();
-    if (threadIdx.x < 10) {
-        double v = 0.0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) v += red[q][threadIdx.x];
-        G[threadIdx.x] = v;
-        gram[threadIdx.x] = v;
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += 256) {
-        const double w0 = w[(int64_t)c * ldw + xcol0], w1 = w[(int64_t)c * ldw + xcol0 + 1], w2 = w[(int64_t)c * ldw + xcol0 + 2];
-        const double b = bias ? (double)bias[c] : 0.0;
-        const double mx = G[0] / M, my = G[1] / M, mz = G[2] / M;
-        // covariance of the inputs (biased), then the variance of y = W x + b: W Cov W^T
-        const double cxx = G[3] / M - mx * mx, cxy = G[4] / M - mx * my, cxz = G[5] / M - mx * mz;
-        const double cyy = G[6] / M - my * my, cyz = G[7] / M - my * mz, czz = G[8] / M - mz * mz;
-        const double mu = w0 * mx + w1 * my + w2 * mz + b;
-        double var = w0 * (w0 * cxx + w1 * cxy + w2 * cxz) + w1 * (w0 * cxy + w1 * cyy + w2 * cyz) + w2 * (w0 * cxz + w1 * cyz + w2 * czz);
-        if (var < 0.0) var = 0.0;
-        const double is = 1.0 / sqrt(var + (double)eps);
-        const double sc = (gamma ? (double)gamma[c] : 1.0) * is;
-        const double sh = (beta ? (double)beta[c] : 0.0) - mu * sc;
-        mean[c] = (float)mu; invstd[c] = (float)is; scale[c] = (float)sc; shift[c] = (float)sh;
-        if (rmean) rmean[c] = momentum * rmean[c] + (1.f - momentum) * (float)mu;     // paddle: momentum weighs the running value
-        if (rvar) rvar[c] = momentum * rvar[c] + (1.f - momentum) * (float)var;
-        // a = relu(scale (W x + b) + shift) = relu(wf . x + t)
-        wf[c * 4 + 0] = (float)(sc * w0); wf[c * 4 + 1] = (float)(sc * w1); wf[c * 4 + 2] = (float)(sc * w2);
-        wf[c * 4 + 3] = (float)(sc * b + sh);
-    }
+    __shared__ double lds[XYZ_L1_FIN_LDS];
+    xyz_l1_finalize_body(lds, a);
 }
 
 // ---- backward: one pass over dz.  A lane owns 4 channels; per row p = dz [wf . x + t > 0]; sums of p and p x -------------------------
@@ -189,70 +154,15 @@ __global__ __launch_bounds__(XYZ_T) void xyz_l1_bwd_kernel(const float *__restri
     }
 }
 
-// partial [parts][C][4] (T0, T1, T2, S) + the input moments -> dgamma, dbeta, dW [C][3]  (closed form, float64).
-// A workgroup owns 4 channels: 16 entries x 64 slices of the partial rows, summed in fixed order.  The kernel is one latency chain (it is the
-// LAST node of the backward): with 64 slices a thread's share of <= 768 partial rows is 12 loads, all in flight at once -- one memory round
-// trip instead of six (17.6 -> ~7 us in the replayed step).
+// partials + the input moments -> dgamma, dbeta, dW [C][3]: the closed form of finalize.h as a launch of its own (the LAST node of a backward
+// that does not defer it to the step's finalize launch, folds.hip)
 __global__ __launch_bounds__(1024) void xyz_l1_bwd_finalize_kernel(const float *__restrict__ partial, int parts, double M, int C, const double *__restrict__ gram,
                                                                    const float *__restrict__ w, int ldw, int xcol0, const float *__restrict__ bias,
                                                                    const float *__restrict__ mean, const float *__restrict__ invstd,
                                                                    const float *__restrict__ scale, float *dgamma, float *dbeta, float *dw, int accumulate)
 {
-    __shared__ double red[64][17], red2[8][17];
-    const int e = threadIdx.x & 15, sl = threadIdx.x >> 4;
-    const int e0 = blockIdx.x * 16;                  // first entry (channel * 4 + slot) of this workgroup
-    const int c = blockIdx.x * 4 + threadIdx.x;
-    const bool fin = threadIdx.x < 4 && c < C;       // (the finalizing threads fetch their constants with the partial rows, not behind the barriers)
-    const int cc = fin ? c : 0;
-    const double w0 = w[(int64_t)cc * ldw + xcol0], w1 = w[(int64_t)cc * ldw + xcol0 + 1], w2 = w[(int64_t)cc * ldw + xcol0 + 2];
-    const double b = bias ? (double)bias[cc] : 0.0;
-    const double mu = mean[cc], is = invstd[cc], sc = scale[cc];
-    double gq[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) gq[i] = gram[i];
-    double s = 0.0;
-    if (e0 + e < C * 4) {
-        for (int t0 = sl; t0 < parts; t0 += 64 * 12) {   // 12 loads in flight per thread
-            float v[12];
-#pragma unroll
-            for (int q = 0; q < 12; ++q) v[q] = (t0 + 64 * q < parts) ? partial[(int64_t)(t0 + 64 * q) * C * 4 + e0 + e] : 0.f;
-#pragma unroll
-            for (int q = 0; q < 12; ++q) s += (double)v[q];
-        }
-    }
-    red[sl][e] = s;
-    __syncthreads();
-    if (sl < 8) {                                    // 64 slices -> 8 -> 1, fixed order
-        double t = 0.0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) t += red[sl * 8 + q][e];
-        red2[sl][e] = t;
-    }
-    __syncthreads();
-    if (sl == 0) {
-        double t = 0.0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) t += red2[q][e];
-        red[0][e] = t;
-    }
-    __syncthreads();
-    if (fin) {
-        const double T0 = red[0][threadIdx.x * 4 + 0], T1 = red[0][threadIdx.x * 4 + 1], T2 = red[0][threadIdx.x * 4 + 2], S = red[0][threadIdx.x * 4 + 3];
-        const double dg = is * (w0 * T0 + w1 * T1 + w2 * T2 + (b - mu) * S);     // sum p xhat
-        dbeta[c] = accumulate ? dbeta[c] + (float)S : (float)S;
-        dgamma[c] = accumulate ? dgamma[c] + (float)dg : (float)dg;
-        const double c1 = S / M, c2 = dg / M;
-        const double Sx[3] = {gq[0], gq[1], gq[2]};
-        const double Sxx[3][3] = {{gq[3], gq[4], gq[5]}, {gq[4], gq[6], gq[7]}, {gq[5], gq[7], gq[8]}};
-        const double T[3] = {T0, T1, T2};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const double yx = w0 * Sxx[0][k] + w1 * Sxx[1][k] + w2 * Sxx[2][k] + (b - mu) * Sx[k];      // sum_m (y - mean) x_k
-            const float gk_ = (float)(sc * (T[k] - c1 * Sx[k] - c2 * is * yx));
-            float *o = dw + (int64_t)c * ldw + xcol0 + k;
-            *o = accumulate ? *o + gk_ : gk_;
-        }
-    }
+    __shared__ double lds[XYZ_BWD_FIN_LDS];
+    xyz_l1_bwd_finalize_body(lds, blockIdx.x, partial, parts, M, C, gram, w, ldw, xcol0, bias, mean, invstd, scale, dgamma, dbeta, dw, accumulate);
 }
 
 }  // namespace papc
@@ -299,8 +209,11 @@ int papc_xyz_l1_finalize_f32(const double *gram_partial, int parts, int64_t M, c
     PAPC_REQUIRE(parts >= 1 && M >= 1 && C >= 1 && ldw >= xcol0 + 3 && xcol0 >= 0, PAPC_E_INVALID, "papc_xyz_l1_finalize_f32: bad sizes");
     hipStream_t st = as_stream(stream);
     ProfScope prof(PAPC_K_MISC, st);
-    hipLaunchKernelGGL(xyz_l1_finalize_kernel, dim3(1), dim3(256), 0, st, gram_partial, parts, (double)M, w, ldw, xcol0, bias, gamma, beta, eps,
-                       momentum, C, mean, invstd, scale, shift, running_mean, running_var, wf, gram);
+    XyzL1Fin a;
+    a.partial = gram_partial; a.parts = parts; a.M = (double)M; a.w = w; a.ldw = ldw; a.xcol0 = xcol0; a.bias = bias; a.gamma = gamma; a.beta = beta;
+    a.eps = eps; a.momentum = momentum; a.C = C; a.mean = mean; a.invstd = invstd; a.scale = scale; a.shift = shift; a.rmean = running_mean;
+    a.rvar = running_var; a.wf = wf; a.gram = gram;
+    hipLaunchKernelGGL(xyz_l1_finalize_kernel, dim3(1), dim3(256), 0, st, a);
     return check_launch("papc_xyz_l1_finalize_f32");
 }
 
@@ -327,6 +240,23 @@ int papc_xyz_l1_bwd_finalize_f32(const float *partial, int parts, int64_t M, int
     hipLaunchKernelGGL(xyz_l1_bwd_finalize_kernel, dim3((unsigned)cdiv(C, 4)), dim3(1024), 0, st, partial, parts, (double)M, C, gram, w, ldw, xcol0, bias, mean, invstd,
                        scale, dgamma, dbeta, dw, accumulate);
     return check_launch("papc_xyz_l1_bwd_finalize_f32");
+}
+
+int papc_xyz_l1_bwd_finalize_defer_f32(const float *partial, int parts, int64_t M, int C, const double *gram, const float *w, int ldw, int xcol0,
+                                       const float *bias, const float *mean, const float *invstd, const float *scale, float *dgamma, float *dbeta,
+                                       float *dw, int accumulate, papc_fold_list *defer, papc_stream_t stream)
+{
+    if (!knob(KNOB_FOLD_FIN) || !fold_list_room(defer, 1 + PAPC_FOLD_FIN_SLOTS))
+        return papc_xyz_l1_bwd_finalize_f32(partial, parts, M, C, gram, w, ldw, xcol0, bias, mean, invstd, scale, dgamma, dbeta, dw, accumulate, stream);
+    PAPC_REQUIRE(partial && gram && w && mean && invstd && scale && dgamma && dbeta && dw, PAPC_E_INVALID, "papc_xyz_l1_bwd_finalize_f32: null pointer");
+    PAPC_REQUIRE(parts >= 1 && M >= 1 && C >= 1 && C <= 256 && ldw >= xcol0 + 3 && xcol0 >= 0, PAPC_E_INVALID, "papc_xyz_l1_bwd_finalize_f32: bad sizes");
+    papc_fold_fin f;
+    memset(&f, 0, sizeof(f));
+    f.kind = PAPC_FIN_XYZ_BWD; f.accumulate = accumulate; f.C = C; f.parts = parts; f.ldw = ldw; f.xcol0 = xcol0; f.M = (double)M;
+    f.src = partial; f.gram = gram; f.w = w; f.bias = bias; f.mean = mean; f.invstd = invstd; f.scale = scale;
+    f.dgamma = dgamma; f.dbeta = dbeta; f.dw = dw;
+    fold_list_push_fin(defer, f);
+    return PAPC_OK;
 }
 
 }  // extern "C"

@@ -7,6 +7,9 @@ graph task id, so that a pass that raised and never ran its callbacks leaves not
 pass registers that list's ``flush`` as a final callback of the autograd engine, which runs it once every node of the pass
 has been enqueued -- still inside a hipGraph capture, and once per stage of a two-stage backward (bench.py, N > 1).  The backward scratch
 buffers the jobs read are kept alive until the fold has been enqueued.  ``PAPC_DEFER_FOLDS=0`` restores the per-stack launches.
+The library also queues what nothing inside the backward waits for: the float64 fold of the no-store max layer's dW and, as finalize
+records behind the folds, that layer's closed form and the coordinates-only first layer's (``FoldFin``; ``PAPC_FOLD_FIN=0``: their
+launches inside the backward) -- papc_fold_jobs_f32 then ends the step in two launches, the folds and the finalizes.
 A module applied twice inside one pass (two augmentations through one model, shared weights) queues two accumulate jobs on the same ``.grad``:
 papc_fold_jobs_f32 applies overlapping jobs in list order, in launches of their own (tests/test_gpu_inplace.py, pattern (d)).
 
@@ -29,6 +32,17 @@ class FoldJob(ctypes.Structure):
     """papc_fold_job"""
     _fields_ = [("partial", ctypes.c_void_p), ("n_chunks", ctypes.c_int32), ("accumulate", ctypes.c_int32), ("ld", ctypes.c_int64),
                 ("rows", ctypes.c_int32), ("cols", ctypes.c_int32), ("out", ctypes.c_void_p), ("out_ld", ctypes.c_int64)]
+
+
+class FoldFin(ctypes.Structure):
+    """papc_fold_fin: a deferred closed-form finalize, which the library stores in the FOLD_FIN_SLOTS job slots behind its header job"""
+    _fields_ = ([("kind", ctypes.c_int32), ("accumulate", ctypes.c_int32), ("C", ctypes.c_int32), ("parts", ctypes.c_int32), ("ldw", ctypes.c_int32),
+                 ("xcol0", ctypes.c_int32), ("M", ctypes.c_double), ("inv_m", ctypes.c_double)]
+                + [(n, ctypes.c_void_p) for n in ("src", "gram", "w", "bias", "mean", "invstd", "scale", "e", "c1", "dgamma", "dbeta", "dw")])
+
+
+FOLD_F64Q, FOLD_FIN = -1, -2            # papc_fold_job.rows of the two kinds of entry beyond the float fold
+FOLD_FIN_SLOTS = -(-ctypes.sizeof(FoldFin) // ctypes.sizeof(FoldJob))
 
 
 class FoldList(ctypes.Structure):
@@ -120,7 +134,7 @@ def pending(keep):
                 old.drop()
     elif p.done or p.stream != _cur_stream():
         return None
-    if p.lst.count > CAPACITY - 16:     # (a stack appends at most 2 jobs per layer + 2)
+    if p.lst.count > CAPACITY - 16:     # (a stack appends at most 2 jobs per layer + 2; its deferred finalizes take 1 + FOLD_FIN_SLOTS slots each where the library finds the room, and launch on their own where not)
         return None
     p.keep.extend(keep)
     return ctypes.pointer(p.lst)

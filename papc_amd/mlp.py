@@ -81,15 +81,33 @@ _XYZ_FUSE = os.environ.get("PAPC_XYZ_FUSE", "1") == "1"   # A/B switch (library 
 # stale transpose can never be picked up.
 
 
-def precompute_wt(weights, feat_blocks=()):
+class WtTable(dict):
+    """precompute_wt's result.  With ``lazy`` the launches are still ``pending``: :meth:`flush` issues them -- the first stack of the forward
+    that runs a coordinates-only first layer through the library (stack.SharedMLPStack) lets the last of them carry that layer's finalize
+    (papc_sa_mlp_xyz1_prep), and the model flushes once more behind that stack (a no-op then) before anything reads the table's tensors."""
+    pending = ()
+
+    def flush(self, l1=None):
+        """``l1`` = (plan, io) of that stack, ``io.saved`` allocated.  True when the finalize rode along."""
+        groups, self.pending = self.pending, ()
+        lib = _lib.load()
+        st = stream_ptr()
+        for i, (srcs, lds, dsts, rws, cls, cps, n) in enumerate(groups):
+            if l1 is not None and i == len(groups) - 1:
+                check(lib.papc_sa_mlp_xyz1_prep(ctypes.byref(l1[0]), ctypes.byref(l1[1]), srcs, lds, dsts, rws, cls, cps, n, st), "papc_sa_mlp_xyz1_prep")
+            else:
+                check(lib.papc_transpose_batch_ld_f32(srcs, lds, dsts, rws, cls, cps, n, st), "papc_transpose_batch_ld_f32")
+        return l1 is not None and bool(groups)
+
+
+def precompute_wt(weights, feat_blocks=(), lazy=False):
     """weights: conv / linear weights [Cout, Cin(, 1...)] whose [Cin, Cout] transposes the coming backward passes will need.
     ``feat_blocks``: (weight [Cout, D + 3(, 1...)], xyz_first) of stacks whose first layer may run as a gather-add: the feature block -- columns
     3.. of an SSG layer's weight (coordinates first), ..D of an MSG branch's -- is made contiguous in the same launch (key
     ``("f", weight.data_ptr())``, value ``(block, xyz_first)``): the copy the stack's forward otherwise launches itself.
+    ``lazy``: the launches wait for :meth:`WtTable.flush` (the caller flushes before the first stack that reads the table).
     Returns the table {weight.data_ptr(): W^T tensor, ...} to pass on as ``StackSpec.wt_table`` for this forward pass only."""
-    lib = _lib.load()
-    st = stream_ptr()
-    table = {}
+    table = WtTable()
     ok = lambda w: w.is_cuda and w.is_contiguous() and w.dtype == torch.float32      # noqa: E731
     jobs = []        # (src pointer, source row stride, destination, rows, cols, copy)
     for w in weights:
@@ -106,6 +124,7 @@ def precompute_wt(weights, feat_blocks=()):
             t = torch.empty(cout, cin - 3, device=w.device, dtype=torch.float32)
             table[("f", w.data_ptr())] = (t, bool(xyz_first))
             jobs.append((w.data_ptr() + (12 if xyz_first else 0), cin, t, cout, cin - 3, 1))
+    groups = []
     for g0 in range(0, len(jobs), 8):
         grp = jobs[g0:g0 + 8]
         n = len(grp)
@@ -113,7 +132,10 @@ def precompute_wt(weights, feat_blocks=()):
         lds, rws, cls, cps = (ctypes.c_int * n)(), (ctypes.c_int * n)(), (ctypes.c_int * n)(), (ctypes.c_int * n)()
         for i, (src, ld, t, rows, cols, cp) in enumerate(grp):
             srcs[i], lds[i], dsts[i], rws[i], cls[i], cps[i] = src, ld, t.data_ptr(), rows, cols, cp
-        check(lib.papc_transpose_batch_ld_f32(srcs, lds, dsts, rws, cls, cps, n, st), "papc_transpose_batch_ld_f32")
+        groups.append((srcs, lds, dsts, rws, cls, cps, n))
+    table.pending = tuple(groups)
+    if not lazy:
+        table.flush()
     return table
 
 

@@ -18,6 +18,7 @@ from .nodeparts import LayerSlots
 
 MAXL = 8
 c_p, c_i, c_l, c_f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+L1_DONE = 4096          # PAPC_SA_L1_DONE
 NO_LINGATHER, NO_XYZ1, NO_NOSTORE, NO_GMAX, NO_FUSED_RED, NO_COMPACT, NO_PLANES, NO_PLANES_POINTWISE, NO_XYZ_FUSE, NO_WSTATS, NO_PSEL, NO_GSIGN = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048
 
 
@@ -173,6 +174,11 @@ class SharedMLPStack(torch.autograd.Function):
         saved = torch.empty(plan.saved_bytes, device=dev, dtype=torch.uint8)
         scratch = torch.empty(plan.fwd_scratch_bytes, device=dev, dtype=torch.uint8)
         io.out, io.saved, io.scratch = out.data_ptr(), saved.data_ptr(), scratch.data_ptr()
+        # a model's weight transposes that still wait for their launch (mlp.precompute_wt(lazy=True)) carry the finalize of a coordinates-only
+        # first layer whose moments came with the sampling plan: one launch less at the head of the step, same bits
+        wt = spec.wt_table
+        if plan.xyz1 and spec.xyz_pre is not None and getattr(wt, "pending", ()) and wt.flush(l1=(plan, io)):
+            plan.d.disable |= L1_DONE
         check(lib.papc_sa_mlp_fwd(ctypes.byref(plan), ctypes.byref(io), stream_ptr()), "papc_sa_mlp_fwd")
         ctx.spec, ctx.L, ctx.plan, ctx.saved = spec, L, plan, saved
         # (diagnostics: which path the library chose for a stack of this shape -- bench.py prices its roofline line on the tensors these
