@@ -976,6 +976,67 @@ int papc_det_post_f32(const papc_det_post_desc *desc, const papc_det_post_io *io
 int papc_box_decode_f32(const float *enc, const float *anchors, int64_t n, int code_size, int encode_angle_to_vector, int smooth_dim,
                         float *out, papc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * PointPillars training targets on the device: the occupied-area anchor mask and TargetAssigner.assign (csrc/dettarget.hip).
+ * data/preprocess.py:251-302 with box_np_ops.py:772-805, target_ops.py:31-214 (the positive_fraction=None path; the sampling path is not
+ * built), similarity_calculator.py:73-93 (NearestIouSimilarity) and box_np_ops.py:30-66 (second_box_encode).  Each entry point is one launch
+ * sequence for the batch: no host synchronisation, no allocation, every output element written.
+ * papc_anchors_mask_u8: coors [P,4] int32 = (batch, z, y, x) -> the count map [B,ny,nx] (rows whose batch index is outside [0, B) are skipped,
+ *   so -1 pads; rows with y or x outside the grid are skipped too; duplicate rows count twice), its inclusive 2-D prefix sums S, and per anchor
+ *   area = S[y2,x2] - S[y2,x1] - S[y1,x2] + S[y1,x1] on cells [A,4] int32 = (x1, y1, x2, y2) -- the source's expression, which leaves out the
+ *   min cell's row and column.  mask [B,A] = area > area_thresh, in integers (exact).  cells are computed by the caller once, inside the grid.
+ * papc_det_assign_f32, per frame b over the anchors whose mask byte is set (all of them with anchors_mask NULL), with G = num_gt[b] held to
+ *   [0, Gmax] (rows >= G of gt_boxes / gt_classes are never read):
+ *   overlap(a, g) = iou_jit(anchors_bv[a], near_bbox(gt_boxes[b,g][0,1,3,4,6]), eps = 0) in canonical fp32 -- r - floor(r / pi + 0.5) pi,
+ *   |.| > pi / 4 swaps w and l, corners c -+ d / 2; iw = min(x2) - max(x1), ih likewise, 0 unless iw > 0 and ih > 0,
+ *   ua = (bx2 - bx1)(by2 - by1) + qarea - iw ih, iou = iw ih / ua -- no fused multiply-add, IEEE division.
+ *   gmax[g] = max over the inside anchors (0 is replaced by -1: such a gt forces nothing); amax / aarg = max / argmax over g, the LOWEST gt
+ *   index on equal overlaps; force = any g with overlap(a, g) == gmax[g].  label = gt_classes[aarg] if force; else 0 if amax < unmatched[a];
+ *   else gt_classes[aarg] if amax >= matched[a]; else -1 (the order the source writes them in).  A forced anchor takes the class and box of
+ *   its OWN argmax gt.  label > 0: reg_targets = second_box_encode(gt_boxes[b,aarg], anchors[a]), reg_weights 1; everything else is zeros.
+ *   Anchors outside the mask: label -1, zeros.  G == 0: label 0 on the inside anchors.
+ *   anchors [A,7], anchors_bv [A,4] (rbbox2d_to_near_bbox of the anchors, cached by the caller), matched / unmatched [A], anchors_mask [B,A]
+ *   bytes or NULL, gt_boxes [B,Gmax,7], gt_classes [B,Gmax] int32, num_gt [B] int32; labels [B,A] int32, reg_targets [B,A,code_size],
+ *   reg_weights [B,A]; optional (NULL skips): gt_ids [B,A] (aarg where label > 0, else -1), max_overlap [B,A] (amax, 0 outside the mask or
+ *   with G == 0), num_pos [B].
+ * Limits (PAPC_E_INVALID before any launch; the _workspace functions return (size_t)-1 and set the message): 1 <= B <= 65535, A >= 1,
+ * B * A < 2^31, 0 <= Gmax <= 256, ny, nx >= 1 with B * ny * nx < 2^31, P >= 0, code_size 8 iff encode_angle_to_vector else 7, null pointers,
+ * coors / cells / anchors_bv 16-byte aligned.
+ * papc_box_encode_f32: second_box_encode of n rows, boxes [n,7], anchors [n,7] -> out [n,code_size]; the counterpart of papc_box_decode_f32. */
+typedef struct papc_anchors_mask_desc {
+    int32_t B, A, ny, nx;
+    int64_t P;
+    float area_thresh;
+    int32_t reserved;
+} papc_anchors_mask_desc;
+typedef struct papc_anchors_mask_io {
+    const int32_t *coors, *cells;
+    uint8_t *mask;
+} papc_anchors_mask_io;
+typedef struct papc_det_assign_desc {
+    int32_t B, A, Gmax, encode_angle_to_vector;
+    int32_t smooth_dim, code_size, reserved0, reserved1;
+} papc_det_assign_desc;
+typedef struct papc_det_assign_io {
+    const float *anchors, *anchors_bv, *matched, *unmatched;
+    const uint8_t *anchors_mask;
+    const float *gt_boxes;
+    const int32_t *gt_classes, *num_gt;
+    int32_t *labels;
+    float *reg_targets, *reg_weights;
+    int32_t *gt_ids;
+    float *max_overlap;
+    int32_t *num_pos;
+} papc_det_assign_io;
+size_t papc_anchors_mask_workspace(const papc_anchors_mask_desc *desc);
+int papc_anchors_mask_u8(const papc_anchors_mask_desc *desc, const papc_anchors_mask_io *io, void *workspace, size_t workspace_bytes,
+                         papc_stream_t stream);
+size_t papc_det_assign_workspace(const papc_det_assign_desc *desc);
+int papc_det_assign_f32(const papc_det_assign_desc *desc, const papc_det_assign_io *io, void *workspace, size_t workspace_bytes,
+                        papc_stream_t stream);
+int papc_box_encode_f32(const float *boxes, const float *anchors, int64_t n, int code_size, int encode_angle_to_vector, int smooth_dim,
+                        float *out, papc_stream_t stream);
+
 /* First layer of a GROUPED stack with the linear map taken before the gather (pointnet2_basic_layers.py:146-153 + conv1 :215-217):
  * a row is [xyz_j - centre | feats_j], so y[m] = P[j] + W_x (xyz_j - centre) + b with P = feats W_f^T [B*N, C] computed once per
  * SOURCE POINT by the caller (a B*N-row GEMM) instead of once per (group, neighbour) row.

@@ -20,6 +20,8 @@ Public surface mirrors the reference:
                           three gradients as one autograd node
   papc_amd.detect      <- PointPillars.predict (detectors/pointpillars.py:218-398) and second_box_decode: score, top-k, box decode and NMS for a
                           whole batch as one launch sequence, counts on the device
+  papc_amd.targets     <- the target half of prep_pointcloud (data/preprocess.py:251-302): the anchor generators, TargetAssigner, the occupied-area
+                          anchor mask and assign() (create_target_np on the nearest-BEV IoU, second_box_encode) for a whole batch on the device
   papc_amd.datasets    <- PAPC/datasets loaders: PNClasDataLoader / PNSegDataLoader / KDClasDataLoader / KDSegDataLoader / VoxDataLoader
 The compute lives in libpapc_hip.so (hand-written HIP, C ABI in include/papc_hip.h).
 """

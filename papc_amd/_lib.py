@@ -143,6 +143,11 @@ SIGNATURES = {
     "papc_det_post_workspace": (ctypes.c_size_t, [c_p]),
     "papc_det_post_f32": (c_i, [c_p, c_p, c_p, ctypes.c_size_t, c_p]),
     "papc_box_decode_f32": (c_i, [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p]),
+    "papc_anchors_mask_workspace": (ctypes.c_size_t, [c_p]),
+    "papc_anchors_mask_u8": (c_i, [c_p, c_p, c_p, ctypes.c_size_t, c_p]),
+    "papc_det_assign_workspace": (ctypes.c_size_t, [c_p]),
+    "papc_det_assign_f32": (c_i, [c_p, c_p, c_p, ctypes.c_size_t, c_p]),
+    "papc_box_encode_f32": (c_i, [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p]),
     "papc_points_to_voxel_workspace": (ctypes.c_size_t, [c_i]),
     "papc_points_to_voxel_f32": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, ctypes.c_size_t, c_p]),
     "papc_pillar_scatter_f32": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),

@@ -179,6 +179,10 @@ int64_t papc_abi_sizeof(const char *struct_name)
     PAPC_SIZEOF(papc_det_loss_io)
     PAPC_SIZEOF(papc_det_post_desc)
     PAPC_SIZEOF(papc_det_post_io)
+    PAPC_SIZEOF(papc_anchors_mask_desc)
+    PAPC_SIZEOF(papc_anchors_mask_io)
+    PAPC_SIZEOF(papc_det_assign_desc)
+    PAPC_SIZEOF(papc_det_assign_io)
     PAPC_SIZEOF(papc_head_fc_layer)
     PAPC_SIZEOF(papc_head_bwd_job)
     PAPC_SIZEOF(papc_pg_wjob)
