@@ -300,6 +300,42 @@ def ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
+def env_switch(name):
+    """an A/B switch of the environment, on unless set to 0; a module reads its own ONCE, at import, into the constant behind its fused_enabled()"""
+    return os.environ.get(name, "1") != "0"
+
+
+_BAD_SIZE = ctypes.c_size_t(-1).value                            # a papc_*_workspace(desc)'s answer to a desc outside the kernels' limits
+
+
+def workspace_bytes(symbol, desc):
+    """bytes the size_t-returning ``symbol`` (a papc_*_workspace taking one desc) asks for; PapcError with the C error text when it refuses the desc"""
+    lib = load()
+    n = int(getattr(lib, symbol)(ctypes.byref(desc)))
+    if n == _BAD_SIZE:
+        raise PapcError(symbol + ": " + lib.papc_last_error_string().decode("utf-8", "replace"))
+    return n
+
+
+def workspace(symbol, desc, device, given=None):
+    """(uint8 tensor, bytes needed): ``given``, the caller's buffer, checked against workspace_bytes(symbol, desc), or a fresh one on ``device``"""
+    import torch
+    n = workspace_bytes(symbol, desc)
+    ws = torch.empty(n, dtype=torch.uint8, device=device) if given is None else given
+    assert ws.dtype == torch.uint8 and ws.is_cuda and ws.numel() >= n, "workspace: %d bytes of uint8 on the device needed" % n
+    return ws, n
+
+
+def outputs(res, table, device):
+    """fill the dict ``res`` from ``table`` of (name, dtype, shape): an entry the caller passed in is checked, a missing one allocated"""
+    import torch
+    for name, dt, shape in table:
+        if name not in res:
+            res[name] = torch.empty(shape, dtype=dt, device=device)
+        assert res[name].shape == shape and res[name].dtype == dt and res[name].is_contiguous(), name
+    return res
+
+
 def cst_ptrs(cst):
     """(mean, invstd, scale, shift): the rows of a layer's [4, C] BatchNorm constants block, as pointers"""
     p, ld = cst.data_ptr(), 4 * cst.stride(0)

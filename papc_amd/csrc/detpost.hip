@@ -8,12 +8,15 @@
 //           behind every passing key of its frame; num_pass[b] by one integer atomic per wave.  No box is decoded here.
 //   order   ONE device-wide descending radix sort (rocPRIM) of keys (B - 1 - b | score | a): frame b's keys land in [b A, (b + 1) A), inside
 //           it by descending score, then descending anchor index -- the order of nms_key_kernel, which the top-k cut and the sweep share
-//   decode  ranks < n_b = min(num_pass[b], K) only: second_box_decode in the source's fp32 operation order, the NMS box, score, label,
-//           direction label
-//   mask    grid (cb, cb, B), cb = ceil(K / 64): the 64-bit ballot word of nms_mask_kernel / rotate_nms_mask_kernel; blocks past n_b and
-//           blocks left of the diagonal (never read by the sweep) exit
-//   sweep   one wave per frame: nms_sweep_kernel's sequential loop, stopped at P kept boxes, then the outputs, padding included
+//   decode  ranks < n_b = min(num_pass[b], K) only: second_box_decode in the source's fp32 operation order (box_decode, box_codec.h), the NMS
+//           box (the rotated one, or its stand-up box: standup_of, nms_iou.h), score, label, direction label
+//   mask    grid (cb, cb, B), cb = ceil(K / 64): nms_mask_tile (nms_iou.h), the tile papc_nms_f32 / papc_rotate_nms_f32 run, on eight
+//           waves; blocks past n_b and blocks left of the diagonal (never read by the sweep) exit
+//   sweep   one wave per frame: nms_sweep (nms_iou.h), the standalone drivers' sequential loop, stopped at P kept boxes, then the outputs,
+//           padding included
+// papc_box_decode_f32, the elementwise decode, is box_codec.h's driver.
 // Nothing here waits on the host: n_b is read from device memory by every kernel that needs it.  -ffp-contract=off.
+#include "box_codec.h"
 #include "carve.h"
 #include "common.h"
 #include "nms_iou.h"
@@ -76,38 +79,6 @@ __global__ __launch_bounds__(256) void dp_score_kernel(DpArgs a)
     }
 }
 
-// second_box_decode (box_paddle_ops.py:48-83), the source's operation order in fp32
-__device__ __forceinline__ void dp_decode(const float *__restrict__ t, const float *__restrict__ an, int angle_vec, int smooth, float *o)
-{
-    const float xa = an[0], ya = an[1], wa = an[3], la = an[4], ha = an[5], ra = an[6];
-    const float za = an[2] + ha / 2.f;                                   // :61
-    const float diagonal = sqrtf(la * la + wa * wa);                     // :62
-    const float xg = t[0] * diagonal + xa, yg = t[1] * diagonal + ya;    // :63-64
-    float zg = t[2] * ha + za;                                           // :65
-    float lg, wg, hg, rg;
-    if (smooth) { lg = (t[4] + 1.f) * la; wg = (t[3] + 1.f) * wa; hg = (t[5] + 1.f) * ha; }        // :66-69
-    else { lg = expf(t[4]) * la; wg = expf(t[3]) * wa; hg = expf(t[5]) * ha; }                     // :70-73
-    if (angle_vec) rg = atan2f(t[7] + sinf(ra), t[6] + cosf(ra));        // :74-79
-    else rg = t[6] + ra;                                                 // :81
-    zg = zg - hg / 2.f;                                                  // :82
-    o[0] = xg; o[1] = yg; o[2] = zg; o[3] = wg; o[4] = lg; o[5] = hg; o[6] = rg;
-}
-
-__global__ __launch_bounds__(256) void dp_box_decode_kernel(const float *__restrict__ enc, const float *__restrict__ anchors, int64_t n, int code,
-                                                            int angle_vec, int smooth, float *__restrict__ out)
-{
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        float t[8], an[7], o[7];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) t[c] = c < code ? enc[i * code + c] : 0.f;
-#pragma unroll
-        for (int c = 0; c < 7; ++c) an[c] = anchors[i * 7 + c];
-        dp_decode(t, an, angle_vec, smooth, o);
-#pragma unroll
-        for (int c = 0; c < 7; ++c) out[i * 7 + c] = o[c];
-    }
-}
-
 __device__ __forceinline__ int dp_nb(const DpArgs &a, int b) { return min(a.io.num_pass[b], a.d.pre_max); }   // nms(): min(len(scores), pre_max_size)
 
 __global__ __launch_bounds__(256) void dp_gather_kernel(DpArgs a)
@@ -124,16 +95,13 @@ __global__ __launch_bounds__(256) void dp_gather_kernel(DpArgs a)
     const float *anchors = a.io.anchors + (int64_t)b * d.anchor_batch_stride + (int64_t)i * 7;
 #pragma unroll
     for (int k = 0; k < 7; ++k) an[k] = anchors[k];
-    dp_decode(t, an, d.encode_angle_to_vector, d.smooth_dim, o);
+    box_decode(t, an, d.encode_angle_to_vector, d.smooth_dim, o);
 #pragma unroll
     for (int k = 0; k < 7; ++k) a.box7[c * 7 + k] = o[k];
     float nb[5] = {o[0], o[1], o[3], o[4], o[6]};                        // box_preds[:, [0, 1, 3, 4, 6]]  (:338)
     if (!d.use_rotate_nms) {                                             // center_to_corner_box2d -> corner_to_standup_nd (:339-344); corners_of
-        const Quad q = corners_of(nb);                                   // is that rotation, term for term (dims * -+0.5, x cos + y sin, + centre)
-        float x0 = q.x[0], y0 = q.y[0], x1 = q.x[0], y1 = q.y[0];
-#pragma unroll
-        for (int k = 1; k < 4; ++k) { x0 = fminf(x0, q.x[k]); y0 = fminf(y0, q.y[k]); x1 = fmaxf(x1, q.x[k]); y1 = fmaxf(y1, q.y[k]); }
-        nb[0] = x0; nb[1] = y0; nb[2] = x1; nb[3] = y1; nb[4] = 0.f;
+        const float4 su = standup_of(corners_of(nb));                    // is that rotation, term for term (dims * -+0.5, x cos + y sin, + centre)
+        nb[0] = su.x; nb[1] = su.y; nb[2] = su.z; nb[3] = su.w; nb[4] = 0.f;
     }
 #pragma unroll
     for (int k = 0; k < 5; ++k) a.nbox[c * 5 + k] = nb[k];
@@ -144,67 +112,30 @@ __global__ __launch_bounds__(256) void dp_gather_kernel(DpArgs a)
     a.aidx[c] = i;
 }
 
-// one workgroup per (row block, column block, frame); lanes = columns.  The words of nms_mask_kernel / rotate_nms_mask_kernel on frame b's n_b
-// candidates.  Those kernels walk a block's 64 rows on one wave; K = 1000 leaves 136 blocks per frame on the diagonal and right of it, and a
-// rotated IoU is a long fp64 chain, so here DP_MASK_WAVES waves share the rows, 64 / DP_MASK_WAVES consecutive ones each (the same ballots).
-constexpr int DP_MASK_WAVES = 8, DP_MASK_ROWS = 64 / DP_MASK_WAVES;
+// one workgroup per (row block, column block, frame): nms_mask_tile (nms_iou.h) on frame b's n_b candidates.  The standalone drivers walk a
+// block's 64 rows on one wave; K = 1000 leaves 136 blocks per frame on the diagonal and right of it, and a rotated IoU is a long fp64 chain, so
+// here DP_MASK_WAVES waves share the rows, 64 / DP_MASK_WAVES consecutive ones each (the same ballots).
+constexpr int DP_MASK_WAVES = 8;
 template <bool ROTATE>
 __global__ __launch_bounds__(64 * DP_MASK_WAVES) void dp_mask_kernel(DpArgs a)
 {
-    const int row_start = blockIdx.y, col_start = blockIdx.x, b = blockIdx.z, lane = lane_id(), wave = threadIdx.x >> 6;
-    const int N = dp_nb(a, b);
-    if (col_start < row_start || col_start * 64 >= N) return;           // left of the diagonal: the sweep reads words from its own block on
-    const float *boxes = a.nbox + (int64_t)b * a.d.pre_max * 5;
-    const float thr = a.d.iou_thresh;
-    __shared__ float rows[64 * 5];
-    const int row_size = min(N - row_start * 64, 64), col_size = min(N - col_start * 64, 64);
-    if (wave == 0 && lane < row_size) {
-#pragma unroll
-        for (int c = 0; c < 5; ++c) rows[lane * 5 + c] = boxes[((int64_t)row_start * 64 + lane) * 5 + c];
-    }
-    float cbx[5] = {0.f, 0.f, 1.f, 1.f, 0.f};
-    if (lane < col_size) {
-#pragma unroll
-        for (int c = 0; c < 5; ++c) cbx[c] = boxes[((int64_t)col_start * 64 + lane) * 5 + c];
-    }
-    __syncthreads();
-    unsigned long long mine = 0;
-    const int row0 = wave * DP_MASK_ROWS, row1 = min(row0 + DP_MASK_ROWS, row_size);
-    for (int i = row0; i < row1; ++i) {
-        const int start = (row_start == col_start) ? i + 1 : 0;
-        bool hit = false;
-        if (lane >= start && lane < col_size) {
-            if (ROTATE) hit = rotate_iou_eval(&rows[i * 5], cbx, -1) > (double)thr;
-            else hit = iou_dev(&rows[i * 5], cbx) > thr;
-        }
-        const unsigned long long t = __ballot(hit);
-        if (lane == i) mine = t;
-    }
-    if (lane >= row0 && lane < row1) a.mask[((int64_t)b * a.d.pre_max + (int64_t)row_start * 64 + lane) * a.cb + col_start] = mine;
+    const int row_start = blockIdx.y, col_start = blockIdx.x, b = blockIdx.z;
+    if (col_start < row_start) return;                                  // left of the diagonal: the sweep reads words from its own block on
+    const int N = dp_nb(a, b);                                          // (those blocks leave before this load)
+    if (col_start * 64 >= N) return;
+    nms_mask_tile<ROTATE, DP_MASK_WAVES>(a.nbox + (int64_t)b * a.d.pre_max * 5, 5, N, a.d.iou_thresh, row_start, col_start,
+                                         a.mask + (int64_t)b * a.d.pre_max * a.cb, a.cb);
 }
 
-// nms_postprocess on one wave per frame (nms_sweep_kernel), stopped at P kept boxes ([:post_max_size], :410), then every output row of the frame
+// nms_postprocess on one wave per frame (nms_sweep, nms_iou.h), stopped at P kept boxes ([:post_max_size], :410), then every output row of the frame
 __global__ __launch_bounds__(64) void dp_sweep_emit_kernel(DpArgs a)
 {
     const papc_det_post_desc &d = a.d;
     __shared__ unsigned long long remv[64];
     __shared__ int kept[4096];
     const int b = blockIdx.x, lane = threadIdx.x, K = d.pre_max, P = d.post_max;
-    const int N = dp_nb(a, b), cbn = (N + 63) >> 6;
-    remv[lane] = 0ull;
-    __syncthreads();
-    int n_keep = 0;
-    for (int i = 0; i < N && n_keep < P; ++i) {
-        const int nblock = i >> 6, inblock = i & 63;
-        const bool removed = (remv[nblock] >> inblock) & 1ull;      // uniform (same LDS word for every lane)
-        if (!removed) {
-            if (lane == 0) kept[n_keep] = i;
-            ++n_keep;
-            const int j = nblock + lane;
-            if (j < cbn) remv[j] |= a.mask[((int64_t)b * K + i) * a.cb + j];
-            __syncthreads();
-        }
-    }
+    const int N = min(dp_nb(a, b), 64 * 64);                        // pre_max <= 4096: said again, so that the sweep's strided loops are one pass
+    const int n_keep = nms_sweep(a.mask + (int64_t)b * K * a.cb, N, a.cb, P, remv, [&](int n, int i) { kept[n] = i; });
     __syncthreads();
     if (lane == 0) a.io.num_det[b] = n_keep;
     const float pi = 3.14159265358979323846f;                       // np.pi cast to the boxes' dtype (:372)
@@ -240,10 +171,8 @@ using namespace papc;
 static int dp_check_desc(const char *who, const papc_det_post_desc *d)
 {
     PAPC_REQUIRE(d, PAPC_E_INVALID, "%s: null pointer", who);
-    PAPC_REQUIRE(d->B >= 1 && d->B <= 65535 && d->A >= 1 && (int64_t)d->B * d->A < ((int64_t)1 << 31), PAPC_E_INVALID,
-                 "%s: B=%d A=%d (need 1 <= B <= 65535, A >= 1 and B * A < 2^31)", who, d->B, d->A);
-    PAPC_REQUIRE(d->code_size == (d->encode_angle_to_vector ? 8 : 7), PAPC_E_INVALID, "%s: code_size=%d with encode_angle_to_vector=%d (8 iff set, else 7)",
-                 who, d->code_size, d->encode_angle_to_vector);
+    if (int rc = require_frames_anchors(who, d->B, d->A)) return rc;
+    if (int rc = require_code_size(who, d->code_size, d->encode_angle_to_vector)) return rc;
     PAPC_REQUIRE(d->score_mode >= 0 && d->score_mode <= 2, PAPC_E_INVALID, "%s: score_mode=%d not in {0, 1, 2}", who, d->score_mode);
     PAPC_REQUIRE(d->num_cls >= (d->score_mode == 0 ? 1 : 2) && d->num_cls <= 16, PAPC_E_INVALID,
                  "%s: num_cls=%d not in [%d, 16] for score_mode %d", who, d->num_cls, d->score_mode == 0 ? 1 : 2, d->score_mode);
@@ -268,7 +197,7 @@ static size_t dp_layout(const papc_det_post_desc *d, void *base, hipStream_t st,
     a.abits = dp_bits(d->A);
     a.cb = (int)cdiv(d->pre_max, 64);
     end_bit = 31 + a.abits + dp_bits(d->B);                              // <= 63: B * A < 2^31
-    WsCarver c{reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255), 0};     // (the caller's base rounded up: 256 of slack)
+    WsCarver c = WsCarver::over(base);
     a.keys = c.take<uint64_t>(BA); a.sorted = c.take<uint64_t>(BA);
     a.nbox = c.take<float>(BK * 5); a.box7 = c.take<float>(BK * 7); a.score = c.take<float>(BK);
     a.label = c.take<int32_t>(BK); a.dirl = c.take<int32_t>(BK); a.aidx = c.take<int32_t>(BK);
@@ -276,7 +205,7 @@ static size_t dp_layout(const papc_det_post_desc *d, void *base, hipStream_t st,
     sort_bytes = 0;
     (void)rocprim::radix_sort_keys_desc(nullptr, sort_bytes, a.keys, a.sorted, BA, 0, end_bit, st);
     tmp = c.take<char>(sort_bytes);
-    return ((c.off + 255) & ~(size_t)255) + 256;
+    return c.bytes();
 }
 
 extern "C" {
@@ -325,16 +254,7 @@ int papc_det_post_f32(const papc_det_post_desc *desc, const papc_det_post_io *io
 int papc_box_decode_f32(const float *enc, const float *anchors, int64_t n, int code_size, int encode_angle_to_vector, int smooth_dim, float *out,
                         papc_stream_t stream)
 {
-    const char *who = "papc_box_decode_f32";
-    PAPC_REQUIRE(enc && anchors && out, PAPC_E_INVALID, "%s: null pointer", who);
-    PAPC_REQUIRE(n >= 1, PAPC_E_INVALID, "%s: n=%lld < 1", who, (long long)n);
-    PAPC_REQUIRE(code_size == (encode_angle_to_vector ? 8 : 7), PAPC_E_INVALID, "%s: code_size=%d with encode_angle_to_vector=%d (8 iff set, else 7)",
-                 who, code_size, encode_angle_to_vector);
-    hipStream_t st = as_stream(stream);
-    ProfScope prof(PAPC_K_MISC, st);
-    hipLaunchKernelGGL(dp_box_decode_kernel, dim3((unsigned)std::min<int64_t>(cdiv(n, 256), 2048)), dim3(256), 0, st, enc, anchors, n, code_size,
-                       encode_angle_to_vector != 0, smooth_dim != 0, out);
-    return check_launch(who);
+    return box_codec_launch<false>("papc_box_decode_f32", enc, anchors, n, code_size, encode_angle_to_vector, smooth_dim, out, stream);
 }
 
 }  // extern "C"

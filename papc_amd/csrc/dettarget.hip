@@ -13,8 +13,12 @@
 //           decide  the G overlaps again per anchor: max / argmax (lowest gt on ties), the force match, the label, second_box_encode
 // Integers make the mask exact.  The overlap is canonical fp32, operation for operation as iou_jit runs on float32 inputs: no fused multiply-add
 // (-ffp-contract=off), IEEE division.  Nothing here waits on the host.
+// The overlap is standup_iou (nms_iou.h, shared with the rbbox_iou / riou pre-test), second_box_encode is box_encode (box_codec.h, beside its
+// inverse); papc_box_encode_f32, the elementwise encode, is box_codec.h's driver.
+#include "box_codec.h"
 #include "carve.h"
 #include "common.h"
+#include "nms_iou.h"
 
 namespace papc {
 
@@ -124,25 +128,14 @@ __device__ __forceinline__ void dt_near_bbox(const float *__restrict__ b7, float
     o[0] = b7[0] - dx / 2.f; o[1] = b7[1] - dy / 2.f; o[2] = b7[0] + dx / 2.f; o[3] = b7[1] + dy / 2.f;
 }
 
-// iou_jit (:654-682) with eps = 0 for one (anchor, gt) pair
-__device__ __forceinline__ float dt_iou(const float4 &an, const float *__restrict__ q, float qarea)
-{
-    const float iw = fminf(an.z, q[2]) - fmaxf(an.x, q[0]);
-    if (!(iw > 0.f)) return 0.f;
-    const float ih = fminf(an.w, q[3]) - fmaxf(an.y, q[1]);
-    if (!(ih > 0.f)) return 0.f;
-    const float ua = (an.z - an.x) * (an.w - an.y) + qarea - iw * ih;
-    return iw * ih / ua;
-}
-
 // the frame's gt near-bboxes and areas into LDS; returns G = num_gt[b] held to [0, Gmax]
-__device__ __forceinline__ int dt_load_gts(const DtArgs &a, int b, float *qbv, float *qarea)
+__device__ __forceinline__ int dt_load_gts(const DtArgs &a, int b, float4 *qbv, float *qarea)
 {
     const int G = min(max(a.io.num_gt[b], 0), a.d.Gmax);
     for (int g = threadIdx.x; g < G; g += blockDim.x) {
         float o[4];
         dt_near_bbox(a.io.gt_boxes + ((int64_t)b * a.d.Gmax + g) * 7, o);
-        qbv[g * 4 + 0] = o[0]; qbv[g * 4 + 1] = o[1]; qbv[g * 4 + 2] = o[2]; qbv[g * 4 + 3] = o[3];
+        qbv[g] = make_float4(o[0], o[1], o[2], o[3]);
         qarea[g] = (o[2] - o[0]) * (o[3] - o[1]);
     }
     return G;
@@ -151,7 +144,8 @@ __device__ __forceinline__ int dt_load_gts(const DtArgs &a, int b, float *qbv, f
 __global__ __launch_bounds__(256) void dt_gmax_kernel(DtArgs a)
 {
     const papc_det_assign_desc &d = a.d;
-    __shared__ float qbv[DT_GMAX * 4], qarea[DT_GMAX];
+    __shared__ float4 qbv[DT_GMAX];
+    __shared__ float qarea[DT_GMAX];
     __shared__ unsigned lmax[DT_GMAX];
     const int b = blockIdx.y;
     const int G = dt_load_gts(a, b, qbv, qarea);
@@ -162,7 +156,7 @@ __global__ __launch_bounds__(256) void dt_gmax_kernel(DtArgs a)
         if (a.io.anchors_mask && a.io.anchors_mask[(int64_t)b * d.A + i] == 0) continue;
         const float4 an = reinterpret_cast<const float4 *>(a.io.anchors_bv)[i];
         for (int g = 0; g < G; ++g) {
-            const unsigned bits = __float_as_uint(dt_iou(an, &qbv[g * 4], qarea[g]));
+            const unsigned bits = __float_as_uint(standup_iou(an, qbv[g], qarea[g]));
             if (bits > lmax[g]) atomicMax(&lmax[g], bits);
         }
     }
@@ -171,41 +165,12 @@ __global__ __launch_bounds__(256) void dt_gmax_kernel(DtArgs a)
         if (lmax[g] != 0u) atomicMax(&a.gmax[(int64_t)b * d.Gmax + g], lmax[g]);
 }
 
-// second_box_encode (box_np_ops.py:30-66), the source's operation order in fp32
-__device__ __forceinline__ void dt_encode(const float *__restrict__ bx, const float *__restrict__ an, int angle_vec, int smooth, float *o)
-{
-    const float xa = an[0], ya = an[1], wa = an[3], la = an[4], ha = an[5], ra = an[6];
-    const float xg = bx[0], yg = bx[1], wg = bx[3], lg = bx[4], hg = bx[5], rg = bx[6];
-    const float zg = bx[2] + hg / 2.f, za = an[2] + ha / 2.f;            // :41-42
-    const float diagonal = sqrtf(la * la + wa * wa);                      // :43
-    o[0] = (xg - xa) / diagonal;                                          // :44-45
-    o[1] = (yg - ya) / diagonal;
-    o[2] = (zg - za) / ha;                                                // :47
-    if (smooth) { o[4] = lg / la - 1.f; o[3] = wg / wa - 1.f; o[5] = hg / ha - 1.f; }               // :48-51
-    else { o[4] = logf(lg / la); o[3] = logf(wg / wa); o[5] = logf(hg / ha); }                      // :52-55
-    if (angle_vec) { o[6] = cosf(rg) - cosf(ra); o[7] = sinf(rg) - sinf(ra); }                      // :56-63
-    else o[6] = rg - ra;                                                  // :65
-}
-
-__global__ __launch_bounds__(256) void dt_box_encode_kernel(const float *__restrict__ boxes, const float *__restrict__ anchors, int64_t n, int code,
-                                                            int angle_vec, int smooth, float *__restrict__ out)
-{
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        float bx[7], an[7], o[8];
-#pragma unroll
-        for (int c = 0; c < 7; ++c) { bx[c] = boxes[i * 7 + c]; an[c] = anchors[i * 7 + c]; }
-        dt_encode(bx, an, angle_vec, smooth, o);
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-            if (c < code) out[i * code + c] = o[c];
-    }
-}
-
 template <bool ANGLE_VEC>      // a template parameter: the sinf / cosf of the angle-vector code stay out of the 7-float kernel
 __global__ __launch_bounds__(256) void dt_decide_kernel(DtArgs a)
 {
     const papc_det_assign_desc &d = a.d;
-    __shared__ float qbv[DT_GMAX * 4], qarea[DT_GMAX], gm[DT_GMAX];
+    __shared__ float4 qbv[DT_GMAX];
+    __shared__ float qarea[DT_GMAX], gm[DT_GMAX];
     __shared__ int32_t qcls[DT_GMAX];
     const int b = blockIdx.y, lane = lane_id(), code = d.code_size;
     const int G = dt_load_gts(a, b, qbv, qarea);
@@ -227,7 +192,7 @@ __global__ __launch_bounds__(256) void dt_decide_kernel(DtArgs a)
                 const float4 an = reinterpret_cast<const float4 *>(a.io.anchors_bv)[i];
                 bool force = false;
                 for (int g = 0; g < G; ++g) {
-                    const float ov = dt_iou(an, &qbv[g * 4], qarea[g]);
+                    const float ov = standup_iou(an, qbv[g], qarea[g]);
                     if (g == 0 || ov > amax) { amax = ov; aarg = g; }     // np.argmax: the first of equal maxima
                     force |= ov == gm[g];
                 }
@@ -239,7 +204,7 @@ __global__ __launch_bounds__(256) void dt_decide_kernel(DtArgs a)
             }
             pos = label > 0;
             float t[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (pos) dt_encode(a.io.gt_boxes + ((int64_t)b * d.Gmax + aarg) * 7, a.io.anchors + (int64_t)i * 7, ANGLE_VEC, d.smooth_dim, t);
+            if (pos) box_encode(a.io.gt_boxes + ((int64_t)b * d.Gmax + aarg) * 7, a.io.anchors + (int64_t)i * 7, ANGLE_VEC, d.smooth_dim, t);
             a.io.labels[o] = label;
 #pragma unroll
             for (int c = 0; c < 8; ++c)                                   // constant indices: t stays in registers
@@ -262,8 +227,7 @@ using namespace papc;
 static int am_check_desc(const char *who, const papc_anchors_mask_desc *d)
 {
     PAPC_REQUIRE(d, PAPC_E_INVALID, "%s: null pointer", who);
-    PAPC_REQUIRE(d->B >= 1 && d->B <= 65535 && d->A >= 1 && (int64_t)d->B * d->A < ((int64_t)1 << 31), PAPC_E_INVALID,
-                 "%s: B=%d A=%d (need 1 <= B <= 65535, A >= 1 and B * A < 2^31)", who, d->B, d->A);
+    if (int rc = require_frames_anchors(who, d->B, d->A)) return rc;
     PAPC_REQUIRE(d->ny >= 1 && d->nx >= 1 && (int64_t)d->B * d->ny * d->nx < ((int64_t)1 << 31), PAPC_E_INVALID,
                  "%s: ny=%d nx=%d (need ny >= 1, nx >= 1 and B * ny * nx < 2^31)", who, d->ny, d->nx);
     PAPC_REQUIRE(d->P >= 0, PAPC_E_INVALID, "%s: P=%lld < 0", who, (long long)d->P);
@@ -274,19 +238,17 @@ static int am_check_desc(const char *who, const papc_anchors_mask_desc *d)
 static size_t am_layout(const papc_anchors_mask_desc *d, void *base, AmArgs &a)
 {
     a.d = *d;
-    WsCarver c{reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255), 0};     // (the caller's base rounded up: 256 of slack)
+    WsCarver c = WsCarver::over(base);
     a.map = c.take<int32_t>((size_t)d->B * d->ny * d->nx);
-    return ((c.off + 255) & ~(size_t)255) + 256;
+    return c.bytes();
 }
 
 static int dt_check_desc(const char *who, const papc_det_assign_desc *d)
 {
     PAPC_REQUIRE(d, PAPC_E_INVALID, "%s: null pointer", who);
-    PAPC_REQUIRE(d->B >= 1 && d->B <= 65535 && d->A >= 1 && (int64_t)d->B * d->A < ((int64_t)1 << 31), PAPC_E_INVALID,
-                 "%s: B=%d A=%d (need 1 <= B <= 65535, A >= 1 and B * A < 2^31)", who, d->B, d->A);
+    if (int rc = require_frames_anchors(who, d->B, d->A)) return rc;
     PAPC_REQUIRE(d->Gmax >= 0 && d->Gmax <= DT_GMAX, PAPC_E_INVALID, "%s: Gmax=%d not in [0, %d]", who, d->Gmax, DT_GMAX);
-    PAPC_REQUIRE(d->code_size == (d->encode_angle_to_vector ? 8 : 7), PAPC_E_INVALID, "%s: code_size=%d with encode_angle_to_vector=%d (8 iff set, else 7)",
-                 who, d->code_size, d->encode_angle_to_vector);
+    if (int rc = require_code_size(who, d->code_size, d->encode_angle_to_vector)) return rc;
     return 0;
 }
 
@@ -294,9 +256,9 @@ static int dt_check_desc(const char *who, const papc_det_assign_desc *d)
 static size_t dt_layout(const papc_det_assign_desc *d, void *base, DtArgs &a)
 {
     a.d = *d;
-    WsCarver c{reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255), 0};
+    WsCarver c = WsCarver::over(base);
     a.gmax = c.take<unsigned>((size_t)d->B * std::max(d->Gmax, 1));
-    return ((c.off + 255) & ~(size_t)255) + 256;
+    return c.bytes();
 }
 
 extern "C" {
@@ -371,16 +333,7 @@ int papc_det_assign_f32(const papc_det_assign_desc *desc, const papc_det_assign_
 int papc_box_encode_f32(const float *boxes, const float *anchors, int64_t n, int code_size, int encode_angle_to_vector, int smooth_dim, float *out,
                         papc_stream_t stream)
 {
-    const char *who = "papc_box_encode_f32";
-    PAPC_REQUIRE(boxes && anchors && out, PAPC_E_INVALID, "%s: null pointer", who);
-    PAPC_REQUIRE(n >= 1, PAPC_E_INVALID, "%s: n=%lld < 1", who, (long long)n);
-    PAPC_REQUIRE(code_size == (encode_angle_to_vector ? 8 : 7), PAPC_E_INVALID, "%s: code_size=%d with encode_angle_to_vector=%d (8 iff set, else 7)",
-                 who, code_size, encode_angle_to_vector);
-    hipStream_t st = as_stream(stream);
-    ProfScope prof(PAPC_K_MISC, st);
-    hipLaunchKernelGGL(dt_box_encode_kernel, dim3((unsigned)std::min<int64_t>(cdiv(n, 256), 2048)), dim3(256), 0, st, boxes, anchors, n, code_size,
-                       encode_angle_to_vector != 0, smooth_dim != 0, out);
-    return check_launch(who);
+    return box_codec_launch<true>("papc_box_encode_f32", boxes, anchors, n, code_size, encode_angle_to_vector, smooth_dim, out, stream);
 }
 
 }  // extern "C"

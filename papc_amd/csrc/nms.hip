@@ -5,9 +5,11 @@
 //
 //   order  = argsort(score) descending                       (radix sort of (ordered score, index) keys, rocPRIM)
 //   mask   = per (row box i, 64-column block) one 64-bit word: bit j set when IoU(box_i, box_j) > thr and j comes after i
-//            -- the reference builds the word with a 64-iteration loop per thread (threadsPerBlock = 64 = one mask word);
-//            on a 64-lane wave the word IS one __ballot over the block's columns
+//            -- nms_mask_tile (nms_iou.h), one wave per tile, every tile of the grid
 //   sweep  = the reference's sequential host loop (keep i unless an earlier kept box removed it), one wave on the device
+//            -- nms_sweep (nms_iou.h), run to the last box
+// The tile and the sweep are the ones papc_det_post_f32 (detpost.hip) runs.  The rotated variant (papc_rotate_nms_f32) and the IoU entry
+// points (rotate_iou, rbbox_iou, riou: the stand-up pre-test is standup_of / standup_iou of nms_iou.h) live here too.
 // IoU in fp32 with the source's "+1" box convention, -ffp-contract=off: the keep decisions are bit-identical to the oracle.
 #include "carve.h"
 #include "common.h"
@@ -32,81 +34,22 @@ __global__ __launch_bounds__(256) void nms_gather_kernel(const float *__restrict
     for (int c = 0; c < W; ++c) sorted[(int64_t)i * W + c] = dets[(int64_t)src * W + c];
 }
 
-// one wave per (row block, column block); lanes = columns
+// one wave per (row block, column block), every tile of the cb x cb grid: nms_mask_tile (nms_iou.h) on the sorted rows, [N,5] =
+// (x1, y1, x2, y2, score) for nms_kernel (:73-108), [N,6] = (x, y, x_d, y_d, angle, score) for rotate_nms_kernel (:417-450)
+template <bool ROTATE>
 __global__ __launch_bounds__(64) void nms_mask_kernel(const float *__restrict__ boxes, int N, float thr, int col_blocks,
                                                       unsigned long long *__restrict__ mask)
 {
-    const int row_start = blockIdx.y, col_start = blockIdx.x, lane = threadIdx.x;
-    __shared__ float rows[64 * 5];
-    const int row_size = min(N - row_start * 64, 64), col_size = min(N - col_start * 64, 64);
-    if (lane < row_size) {
-#pragma unroll
-        for (int c = 0; c < 5; ++c) rows[lane * 5 + c] = boxes[((int64_t)row_start * 64 + lane) * 5 + c];
-    }
-    float cb[4] = {0.f, 0.f, 0.f, 0.f};
-    if (lane < col_size) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) cb[c] = boxes[((int64_t)col_start * 64 + lane) * 5 + c];
-    }
-    __syncthreads();
-    unsigned long long mine = 0;
-    for (int i = 0; i < row_size; ++i) {
-        const int start = (row_start == col_start) ? i + 1 : 0;                                   // :96-98
-        const bool hit = lane >= start && lane < col_size && iou_dev(&rows[i * 5], cb) > thr;      // :99-102
-        const unsigned long long t = __ballot(hit);
-        if (lane == i) mine = t;
-    }
-    if (lane < row_size) mask[((int64_t)row_start * 64 + lane) * col_blocks + col_start] = mine;  // :105
+    nms_mask_tile<ROTATE, 1>(boxes, ROTATE ? 6 : 5, N, thr, blockIdx.y, blockIdx.x, mask, col_blocks);
 }
 
-// nms_postprocess (:111-127) on one wave: remv words live in LDS, lanes OR a kept row's words in parallel
+// nms_postprocess (:111-127) on one wave: nms_sweep (nms_iou.h) over all N boxes, remv words in dynamic LDS
 __global__ __launch_bounds__(64) void nms_sweep_kernel(const unsigned long long *__restrict__ mask, const int32_t *__restrict__ order, int N,
                                                        int col_blocks, int32_t *__restrict__ keep, int32_t *__restrict__ num_out)
 {
     extern __shared__ unsigned long long remv[];
-    const int lane = threadIdx.x;
-    for (int j = lane; j < col_blocks; j += 64) remv[j] = 0ull;
-    __syncthreads();
-    int n_keep = 0;
-    for (int i = 0; i < N; ++i) {
-        const int nblock = i >> 6, inblock = i & 63;
-        const bool removed = (remv[nblock] >> inblock) & 1ull;      // uniform (same LDS word for every lane)
-        if (!removed) {
-            if (lane == 0) keep[n_keep] = order[i];                 // list(order[keep])  (:164)
-            ++n_keep;
-            for (int j = nblock + lane; j < col_blocks; j += 64) remv[j] |= mask[(int64_t)i * col_blocks + j];
-            __syncthreads();
-        }
-    }
-    if (lane == 0) num_out[0] = n_keep;
-}
-
-// rotate_nms_kernel (:417-450) in the ballot form of nms_mask_kernel; boxes [N,6] = (x, y, x_d, y_d, angle, score)
-__global__ __launch_bounds__(64) void rotate_nms_mask_kernel(const float *__restrict__ boxes, int N, float thr, int col_blocks,
-                                                             unsigned long long *__restrict__ mask)
-{
-    const int row_start = blockIdx.y, col_start = blockIdx.x, lane = threadIdx.x;
-    __shared__ float rows[64 * 5];
-    const int row_size = min(N - row_start * 64, 64), col_size = min(N - col_start * 64, 64);
-    if (lane < row_size) {
-#pragma unroll
-        for (int c = 0; c < 5; ++c) rows[lane * 5 + c] = boxes[((int64_t)row_start * 64 + lane) * 6 + c];
-    }
-    float cb[5] = {0.f, 0.f, 1.f, 1.f, 0.f};
-    if (lane < col_size) {
-#pragma unroll
-        for (int c = 0; c < 5; ++c) cb[c] = boxes[((int64_t)col_start * 64 + lane) * 6 + c];
-    }
-    __syncthreads();
-    unsigned long long mine = 0;
-    for (int i = 0; i < row_size; ++i) {
-        const int start = (row_start == col_start) ? i + 1 : 0;
-        bool hit = false;
-        if (lane >= start && lane < col_size) hit = rotate_iou_eval(&rows[i * 5], cb, -1) > (double)thr;   // devRotateIoU(cur, block_box) (:443-446)
-        const unsigned long long t = __ballot(hit);
-        if (lane == i) mine = t;
-    }
-    if (lane < row_size) mask[((int64_t)row_start * 64 + lane) * col_blocks + col_start] = mine;
+    const int n_keep = nms_sweep(mask, N, col_blocks, N, remv, [&](int n, int i) { keep[n] = order[i]; });   // list(order[keep])  (:164)
+    if (threadIdx.x == 0) num_out[0] = n_keep;
 }
 
 // rotate_iou_kernel(_eval) (:491-521, :577-615): iou[n, k] = devRotateIoUEval(query[k], boxes[n], criterion)
@@ -152,18 +95,8 @@ __global__ __launch_bounds__(256) void rbbox_iou_kernel(const float *__restrict_
     float su;
     if (CORNERS && standup_iou) su = standup_iou[e];
     else {
-        float p0 = P.x[0], p1 = P.y[0], p2 = P.x[0], p3 = P.y[0], q0 = Q.x[0], q1 = Q.y[0], q2 = Q.x[0], q3 = Q.y[0];
-#pragma unroll
-        for (int i = 1; i < 4; ++i) {
-            p0 = fminf(p0, P.x[i]); p1 = fminf(p1, P.y[i]); p2 = fmaxf(p2, P.x[i]); p3 = fmaxf(p3, P.y[i]);
-            q0 = fminf(q0, Q.x[i]); q1 = fminf(q1, Q.y[i]); q2 = fmaxf(q2, Q.x[i]); q3 = fmaxf(q3, Q.y[i]);
-        }
-        su = 0.f;
-        const float iw = fminf(p2, q2) - fmaxf(p0, q0);
-        if (iw > 0.f) {
-            const float ih = fminf(p3, q3) - fmaxf(p1, q1);
-            if (ih > 0.f) su = iw * ih / ((p2 - p0) * (p3 - p1) + (q2 - q0) * (q3 - q1) - iw * ih);
-        }
+        const float4 p = standup_of(P), q = standup_of(Q);
+        su = papc::standup_iou(p, q, (q.z - q.x) * (q.w - q.y));      // (the parameter of that name is the caller's precomputed matrix)
     }
     float out = 0.f;
     if (su > standup_thresh) {
@@ -186,13 +119,13 @@ extern "C" {
 struct NmsPtrs { uint64_t *keys, *sorted_keys; float *boxes; int32_t *order; unsigned long long *mask; void *tmp; size_t sort_bytes = 0; };
 static size_t nms_layout(int N, void *base, hipStream_t st, NmsPtrs &p)
 {
-    WsCarver c{reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255), 0};     // (the caller's base rounded up: 256 of slack)
+    WsCarver c = WsCarver::over(base);
     p.keys = c.take<uint64_t>((size_t)N); p.sorted_keys = c.take<uint64_t>((size_t)N);
     p.boxes = c.take<float>((size_t)N * 6); p.order = c.take<int32_t>((size_t)N);
     p.mask = c.take<unsigned long long>((size_t)N * cdiv(N, 64));
     (void)rocprim::radix_sort_keys_desc(nullptr, p.sort_bytes, p.keys, p.sorted_keys, (size_t)N, 0, 64, st);
     p.tmp = c.take<char>(p.sort_bytes);
-    return ((c.off + 255) & ~(size_t)255) + 256;
+    return c.bytes();
 }
 
 size_t papc_nms_workspace(int N)
@@ -216,8 +149,8 @@ static int nms_driver(const float *dets, int N, int W, float thr, int32_t *keep,
     // descending (score, index): scores.argsort()[::-1] with a stable sort (:145, :469)
     if (rocprim::radix_sort_keys_desc(p.tmp, p.sort_bytes, p.keys, p.sorted_keys, (size_t)N, 0, 64, st) != hipSuccess) return check_launch(who);
     hipLaunchKernelGGL(nms_gather_kernel, dim3(nb), dim3(256), 0, st, dets, p.sorted_keys, N, W, p.boxes, p.order);
-    if (W == 5) hipLaunchKernelGGL(nms_mask_kernel, dim3((unsigned)cb, (unsigned)cb), dim3(64), 0, st, p.boxes, N, thr, cb, p.mask);
-    else hipLaunchKernelGGL(rotate_nms_mask_kernel, dim3((unsigned)cb, (unsigned)cb), dim3(64), 0, st, p.boxes, N, thr, cb, p.mask);
+    if (W == 5) hipLaunchKernelGGL(nms_mask_kernel<false>, dim3((unsigned)cb, (unsigned)cb), dim3(64), 0, st, p.boxes, N, thr, cb, p.mask);
+    else hipLaunchKernelGGL(nms_mask_kernel<true>, dim3((unsigned)cb, (unsigned)cb), dim3(64), 0, st, p.boxes, N, thr, cb, p.mask);
     hipLaunchKernelGGL(nms_sweep_kernel, dim3(1), dim3(64), (size_t)cb * 8, st, p.mask, p.order, N, cb, keep, num_out);
     return check_launch(who);
 }

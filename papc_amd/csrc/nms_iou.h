@@ -1,5 +1,8 @@
-// nms_iou.h -- the IoU device code of the NMS family, once: the order-preserving score key, the axis-aligned "+1" IoU and the rotated-box
-// clipping routines.  Included by nms.hip (papc_nms_f32, papc_rotate_nms_f32, the IoU entry points) and detpost.hip (papc_det_post_f32).
+// nms_iou.h -- the device code of the NMS family, once: the order-preserving score key, the axis-aligned "+1" IoU, the rotated-box clipping
+// routines, the stand-up box of a quadrilateral with its eps = 0 IoU (standup_of, standup_iou), and the two halves of bitmask NMS -- the
+// 64x64 suppression-word tile (nms_mask_tile) and the sequential sweep over the words (nms_sweep).  Included by nms.hip (papc_nms_f32,
+// papc_rotate_nms_f32: the tile on one wave, the sweep to the end; the IoU entry points), detpost.hip (papc_det_post_f32: the tile on
+// DP_MASK_WAVES waves, the sweep stopped at post_max) and dettarget.hip (standup_iou is the assigner's similarity).
 #pragma once
 #include "common.h"
 
@@ -130,6 +133,91 @@ __device__ __forceinline__ double rotate_iou_eval(const float *b1, const float *
     if (criterion == 0) return ai / (double)area1;
     if (criterion == 1) return ai / (double)area2;
     return ai;
+}
+
+// corner_to_standup_nd (box_np_ops.py:236-241, box_paddle_ops.py:202-209): the axis-aligned bounding box (x0, y0, x1, y1) of four corners
+__device__ __forceinline__ float4 standup_of(const Quad &q)
+{
+    float x0 = q.x[0], y0 = q.y[0], x1 = q.x[0], y1 = q.y[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k) { x0 = fminf(x0, q.x[k]); y0 = fminf(y0, q.y[k]); x1 = fmaxf(x1, q.x[k]); y1 = fmaxf(y1, q.y[k]); }
+    return make_float4(x0, y0, x1, y1);
+}
+
+// iou_jit (box_np_ops.py:654-682) with eps = 0 for one pair of (x0, y0, x1, y1) boxes, operation for operation as it runs on float32 inputs;
+// qarea = (q.z - q.x) * (q.w - q.y), which a caller with many boxes against one q forms once
+__device__ __forceinline__ float standup_iou(const float4 &a, const float4 &q, float qarea)
+{
+    const float iw = fminf(a.z, q.z) - fmaxf(a.x, q.x);
+    if (!(iw > 0.f)) return 0.f;
+    const float ih = fminf(a.w, q.w) - fmaxf(a.y, q.y);
+    if (!(ih > 0.f)) return 0.f;
+    const float ua = (a.z - a.x) * (a.w - a.y) + qarea - iw * ih;
+    return iw * ih / ua;
+}
+
+// ---- bitmask NMS (nms_gpu.py:73-108 nms_kernel, :417-450 rotate_nms_kernel, :111-127 nms_postprocess) on boxes sorted by descending score ----
+
+// One (row block, column block) tile of suppression words: bit j of row i's word is set when IoU(box_i, box_j) > thr and, on the diagonal
+// tile, j comes after i.  The reference builds the word with a 64-iteration loop per thread (threadsPerBlock = 64 = one mask word); on a
+// 64-lane wave the word IS one __ballot over the block's columns.  A workgroup of WAVES waves runs the tile: 64 row boxes staged in LDS,
+// one column box per lane, 64 / WAVES consecutive rows per wave (the same ballots whatever WAVES is).  boxes: row_stride floats per box, the
+// first five (x0, y0, x1, y1, -) or (x, y, x_d, y_d, angle); mask_row0: the word of (row 0, block 0).  Which tiles run is the caller's business.
+template <bool ROTATE, int WAVES>
+__device__ __forceinline__ void nms_mask_tile(const float *__restrict__ boxes, int row_stride, int N, float thr, int row_start, int col_start,
+                                              unsigned long long *__restrict__ mask_row0, int col_blocks)
+{
+    constexpr int ROWS = 64 / WAVES;
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    __shared__ float rows[64 * 5];
+    const int row_size = min(N - row_start * 64, 64), col_size = min(N - col_start * 64, 64);
+    if (wave == 0 && lane < row_size) {
+#pragma unroll
+        for (int c = 0; c < 5; ++c) rows[lane * 5 + c] = boxes[((int64_t)row_start * 64 + lane) * row_stride + c];
+    }
+    float cb[5] = {0.f, 0.f, 1.f, 1.f, 0.f};
+    if (lane < col_size) {
+#pragma unroll
+        for (int c = 0; c < 5; ++c) cb[c] = boxes[((int64_t)col_start * 64 + lane) * row_stride + c];
+    }
+    __syncthreads();
+    unsigned long long mine = 0;
+    const int row0 = wave * ROWS, row1 = min(row0 + ROWS, row_size);
+    for (int i = row0; i < row1; ++i) {
+        const int start = (row_start == col_start) ? i + 1 : 0;                                   // :96-98
+        bool hit = false;
+        if (lane >= start && lane < col_size) {
+            if (ROTATE) hit = rotate_iou_eval(&rows[i * 5], cb, -1) > (double)thr;                // devRotateIoU(cur, block_box) (:443-446)
+            else hit = iou_dev(&rows[i * 5], cb) > thr;                                           // :99-102
+        }
+        const unsigned long long t = __ballot(hit);
+        if (lane == i) mine = t;
+    }
+    if (lane >= row0 && lane < row1) mask_row0[((int64_t)row_start * 64 + lane) * col_blocks + col_start] = mine;   // :105
+}
+
+// nms_postprocess (:111-127) on one wave (64 threads): keep box i unless an earlier kept box removed it, until `limit` are kept.  mask: the
+// tiles' words, col_blocks per row -- only the words from a row's own block on are read, up to block ceil(N / 64) - 1.  remv: the caller's
+// LDS, ceil(N / 64) words, zeroed here; lanes OR a kept row's words in parallel.  record(n, i), called by lane 0: box i is the n-th kept.
+template <class Record>
+__device__ __forceinline__ int nms_sweep(const unsigned long long *__restrict__ mask, int N, int col_blocks, int limit, unsigned long long *remv,
+                                         Record record)
+{
+    const int lane = threadIdx.x, words = (N + 63) >> 6;
+    for (int j = lane; j < words; j += 64) remv[j] = 0ull;
+    __syncthreads();
+    int n_keep = 0;
+    for (int i = 0; i < N && n_keep < limit; ++i) {
+        const int nblock = i >> 6, inblock = i & 63;
+        const bool removed = (remv[nblock] >> inblock) & 1ull;      // uniform (same LDS word for every lane)
+        if (!removed) {
+            if (lane == 0) record(n_keep, i);
+            ++n_keep;
+            for (int j = nblock + lane; j < words; j += 64) remv[j] |= mask[(int64_t)i * col_blocks + j];
+            __syncthreads();                                        // in a branch every lane takes or none does: `removed` is uniform
+        }
+    }
+    return n_keep;
 }
 
 }  // namespace papc

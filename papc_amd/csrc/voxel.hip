@@ -156,13 +156,13 @@ static int fill_grid(VoxGrid &v, const float *voxel_size, const float *coors_ran
 struct VoxPtrs { uint64_t *keys, *sorted; int32_t *flag, *before, *cut; void *tmp; size_t sort_bytes = 0, scan_bytes = 0; };
 static size_t vox_layout(int N, void *base, hipStream_t st, VoxPtrs &p)
 {
-    WsCarver c{reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255), 0};     // (the caller's base rounded up: 256 of slack)
+    WsCarver c = WsCarver::over(base);
     p.keys = c.take<uint64_t>((size_t)N); p.sorted = c.take<uint64_t>((size_t)N);
     p.flag = c.take<int32_t>((size_t)N); p.before = c.take<int32_t>((size_t)N); p.cut = c.take<int32_t>(64);
     (void)rocprim::radix_sort_keys(nullptr, p.sort_bytes, p.keys, p.sorted, (size_t)N, 0, 64, st);
     (void)rocprim::exclusive_scan(nullptr, p.scan_bytes, p.flag, p.before, 0, (size_t)N, rocprim::plus<int32_t>(), st);
     p.tmp = c.take<char>(std::max(p.sort_bytes, p.scan_bytes));
-    return ((c.off + 255) & ~(size_t)255) + 256;
+    return c.bytes();
 }
 
 extern "C" {

@@ -23,12 +23,12 @@ as the source does; it is the A/B leg and the fallback for shapes the fused path
 """
 import ctypes
 import math
-import os
 
 import torch
 
-from . import _lib
+from . import _lib, boxcodec
 from . import nms as _nms
+from .boxcodec import _decode_torch
 from ._lib import c_p, c_f, check, ptr, stream_ptr
 
 
@@ -47,9 +47,7 @@ class DetPostIo(ctypes.Structure):
                 ("boxes", c_p), ("scores", c_p), ("labels", c_p), ("dir_labels", c_p), ("anchor_idx", c_p), ("num_det", c_p), ("num_pass", c_p)]
 
 
-_BAD_SIZE = ctypes.c_size_t(-1).value                            # papc_det_post_workspace's answer to a desc outside the limits
-
-_DET_POST = os.environ.get("PAPC_DET_POST", "1") != "0"          # A/B switch: 0 = the source's op sequence in torch ops
+_DET_POST = _lib.env_switch("PAPC_DET_POST")                     # A/B switch: 0 = the source's op sequence in torch ops
 
 OUTPUTS = (("boxes", torch.float32, (7,)), ("scores", torch.float32, ()), ("labels", torch.int32, ()), ("dir_labels", torch.int32, ()),
            ("anchor_idx", torch.int32, ()))
@@ -60,46 +58,10 @@ def fused_enabled():
     return _DET_POST
 
 
-def _decode_torch(t, a, encode_angle_to_vector, smooth_dim):
-    """second_box_decode (box_paddle_ops.py:48-83), op for op"""
-    xa, ya, za, wa, la, ha, ra = torch.split(a, 1, dim=-1)
-    if encode_angle_to_vector:
-        xt, yt, zt, wt, lt, ht, rtx, rty = torch.split(t, 1, dim=-1)
-    else:
-        xt, yt, zt, wt, lt, ht, rt = torch.split(t, 1, dim=-1)
-    za = za + ha / 2
-    diagonal = torch.sqrt(la ** 2 + wa ** 2)
-    xg = xt * diagonal + xa
-    yg = yt * diagonal + ya
-    zg = zt * ha + za
-    if smooth_dim:
-        lg, wg, hg = (lt + 1) * la, (wt + 1) * wa, (ht + 1) * ha
-    else:
-        lg, wg, hg = torch.exp(lt) * la, torch.exp(wt) * wa, torch.exp(ht) * ha
-    if encode_angle_to_vector:
-        rg = torch.atan2(rty + torch.sin(ra), rtx + torch.cos(ra))
-    else:
-        rg = rt + ra
-    zg = zg - hg / 2
-    return torch.cat([xg, yg, zg, wg, lg, hg, rg], dim=-1)
-
-
 def second_box_decode(box_encodings, anchors, encode_angle_to_vector=False, smooth_dim=False, fused=None):
-    """box_paddle_ops.py:48: box_encodings [..., 7] ([..., 8] with encode_angle_to_vector), anchors [..., 7] -> boxes [..., 7] (x, y, z, w, l, h, r)."""
-    code = 8 if encode_angle_to_vector else 7
-    assert box_encodings.shape[-1] == code and anchors.shape[-1] == 7, "box_encodings [..., %d] and anchors [..., 7] expected" % code
-    if not (fused_enabled() if fused is None else fused):
-        return _decode_torch(box_encodings, anchors.expand(box_encodings.shape[:-1] + (7,)), encode_angle_to_vector, smooth_dim)
-    if not box_encodings.is_cuda or not anchors.is_cuda:
-        raise _lib.PapcError("second_box_decode needs CUDA (ROCm) tensors: there is no CPU fallback (PAPC_DET_POST=0 selects the torch-op flavour)")
-    enc = box_encodings.contiguous().float()
-    anc = anchors.expand(enc.shape[:-1] + (7,)).contiguous().float()
-    out = torch.empty(enc.shape[:-1] + (7,), dtype=torch.float32, device=enc.device)
-    n = out.numel() // 7
-    if n:
-        check(_lib.load().papc_box_decode_f32(ptr(enc), ptr(anc), n, code, int(bool(encode_angle_to_vector)), int(bool(smooth_dim)), ptr(out),
-                                              stream_ptr()), "papc_box_decode_f32")
-    return out
+    """box_paddle_ops.py:48: box_encodings [..., 7] ([..., 8] with encode_angle_to_vector), anchors [..., 7] -> boxes [..., 7] (x, y, z, w, l, h, r);
+    boxcodec.second_box_decode under this module's switch."""
+    return boxcodec.second_box_decode(box_encodings, anchors, encode_angle_to_vector, smooth_dim, fused_enabled() if fused is None else fused)
 
 
 def _score_mode(encode_background_as_zeros, use_sigmoid_score):
@@ -113,11 +75,7 @@ def workspace_bytes(B, A, num_cls, nms_pre_max_size, nms_post_max_size, score_mo
     """bytes of workspace one predict_tensors call of this shape needs (papc_det_post_workspace); raises PapcError outside the kernels' limits"""
     d = DetPostDesc(B=B, A=A, num_cls=num_cls, score_mode=score_mode, encode_angle_to_vector=int(bool(encode_angle_to_vector)),
                     code_size=8 if encode_angle_to_vector else 7, pre_max=nms_pre_max_size, post_max=nms_post_max_size)
-    lib = _lib.load()
-    n = int(lib.papc_det_post_workspace(ctypes.byref(d)))
-    if n == _BAD_SIZE:
-        raise _lib.PapcError("papc_det_post_workspace: " + lib.papc_last_error_string().decode("utf-8", "replace"))
-    return n
+    return _lib.workspace_bytes("papc_det_post_workspace", d)
 
 
 def _torch_frame(box, cls, dirp, anc, mask, mode, thresh, use_dir, rotate, K, P, iou, angle_vec, smooth):
@@ -194,15 +152,8 @@ def predict_tensors(box_preds, cls_preds, dir_cls_preds, anchors, anchors_mask=N
     use_fused = fused_enabled() if fused is None else fused
     if use_fused and not (box.is_cuda and cls.is_cuda and anc.is_cuda):
         raise _lib.PapcError("predict needs CUDA (ROCm) tensors: there is no CPU fallback (PAPC_DET_POST=0 selects the torch-op flavour)")
-    res = {} if out is None else out
-    for name, dt, tail in OUTPUTS:
-        if name not in res:
-            res[name] = torch.empty((B, P) + tail, dtype=dt, device=dev)
-        assert res[name].shape == (B, P) + tail and res[name].dtype == dt and res[name].is_contiguous(), name
-    for name in ("num_det", "num_pass"):
-        if name not in res:
-            res[name] = torch.empty(B, dtype=torch.int32, device=dev)
-        assert res[name].shape == (B,) and res[name].dtype == torch.int32, name
+    res = _lib.outputs({} if out is None else out, [(name, dt, (B, P) + tail) for name, dt, tail in OUTPUTS]
+                       + [("num_det", torch.int32, (B,)), ("num_pass", torch.int32, (B,))], dev)
 
     if not use_fused:
         box, cls, anc = box.float(), cls.float(), anc.float()
@@ -227,11 +178,7 @@ def predict_tensors(box_preds, cls_preds, dir_cls_preds, anchors, anchors_mask=N
                     encode_angle_to_vector=int(bool(encode_angle_to_vector)), smooth_dim=int(bool(smooth_dim)), code_size=code, pre_max=K,
                     post_max=P, score_thresh=float(nms_score_threshold), iou_thresh=float(nms_iou_threshold),
                     anchor_batch_stride=0 if shared else A * 7)
-    ws_bytes = int(lib.papc_det_post_workspace(ctypes.byref(d)))
-    if ws_bytes == _BAD_SIZE:
-        raise _lib.PapcError("papc_det_post_workspace: " + lib.papc_last_error_string().decode("utf-8", "replace"))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if workspace is None else workspace
-    assert ws.dtype == torch.uint8 and ws.is_cuda and ws.numel() >= ws_bytes, "workspace: %d bytes of uint8 on the device needed" % ws_bytes
+    ws, _ = _lib.workspace("papc_det_post_workspace", d, dev, workspace)
     io = DetPostIo(box_preds=ptr(box), cls_preds=ptr(cls), dir_preds=ptr(dirp), anchors=ptr(anc), anchors_mask=ptr(mask),
                    boxes=ptr(res["boxes"]), scores=ptr(res["scores"]), labels=ptr(res["labels"]), dir_labels=ptr(res["dir_labels"]),
                    anchor_idx=ptr(res["anchor_idx"]), num_det=ptr(res["num_det"]), num_pass=ptr(res["num_pass"]))

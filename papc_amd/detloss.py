@@ -10,7 +10,6 @@ captured graph.  Sums are folded in a fixed order (csrc/fold.h), so the same inp
 its loss classes restated in torch ops, under their own names and argument lists below.  They take tensors of any device and float dtype.
 """
 import ctypes
-import os
 
 import torch
 import torch.nn.functional as F
@@ -38,7 +37,7 @@ class DetLossIo(ctypes.Structure):
                 ("workspace", c_p)]
 
 
-_DET_LOSS = os.environ.get("PAPC_DET_LOSS", "1") != "0"          # A/B switch: 0 = the loss in torch ops
+_DET_LOSS = _lib.env_switch("PAPC_DET_LOSS")                     # A/B switch: 0 = the loss in torch ops
 
 
 def fused_enabled():

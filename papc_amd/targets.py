@@ -23,12 +23,12 @@ ground-truth rows per frame (``Gmax``).
 vectorised float32 torch ops in the same operation order, frame by frame, with host synchronisation.  It is the A/B leg and runs on CPU tensors too.
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, boxcodec
+from .boxcodec import _const, _encode_torch
 from ._lib import c_p, c_f, check, ptr, stream_ptr
 
 
@@ -56,9 +56,7 @@ class DetAssignIo(ctypes.Structure):
                 ("max_overlap", c_p), ("num_pos", c_p)]
 
 
-_BAD_SIZE = ctypes.c_size_t(-1).value                            # the _workspace functions' answer to a desc outside the limits
-
-_DET_TARGETS = os.environ.get("PAPC_DET_TARGETS", "1") != "0"    # A/B switch: 0 = the torch-op flavour
+_DET_TARGETS = _lib.env_switch("PAPC_DET_TARGETS")               # A/B switch: 0 = the torch-op flavour
 
 GMAX_LIMIT = 256
 
@@ -138,11 +136,6 @@ class AnchorGeneratorRange(_AnchorGenerator):
         r = np.array(self._anchor_ranges, self._dtype)
         z, y, x = (np.linspace(r[2 - k], r[5 - k], feature_map_size[k], dtype=self._dtype) for k in range(3))
         return _anchor_grid(z, y, x, self._sizes, self._rotations, self._dtype)
-
-
-def _const(value, like):
-    """a 0-dim tensor on ``like``'s device: an operand, so that x / c is a division on every backend, never a product with a reciprocal"""
-    return torch.tensor(value, dtype=like.dtype, device=like.device)
 
 
 def rbbox2d_to_near_bbox(rbboxes):
@@ -235,11 +228,7 @@ def anchor_cache(assigner, feature_map_size, voxel_size, point_cloud_range, grid
 
 def mask_workspace_bytes(B, A, ny, nx):
     """bytes of workspace one anchors_mask call of this shape needs (papc_anchors_mask_workspace); raises PapcError outside the kernels' limits"""
-    lib = _lib.load()
-    n = int(lib.papc_anchors_mask_workspace(ctypes.byref(AnchorsMaskDesc(B=B, A=A, ny=ny, nx=nx))))
-    if n == _BAD_SIZE:
-        raise _lib.PapcError("papc_anchors_mask_workspace: " + lib.papc_last_error_string().decode("utf-8", "replace"))
-    return n
+    return _lib.workspace_bytes("papc_anchors_mask_workspace", AnchorsMaskDesc(B=B, A=A, ny=ny, nx=nx))
 
 
 def _mask_torch(coors, B, cells, nx, ny, thresh):
@@ -275,11 +264,7 @@ def anchors_mask(coors, batch_size, cache, anchor_area_threshold=1, out=None, wo
     coors = coors.int().contiguous()
     lib = _lib.load()
     d = AnchorsMaskDesc(B=B, A=A, ny=ny, nx=nx, P=int(coors.shape[0]), area_thresh=float(anchor_area_threshold))
-    ws_bytes = int(lib.papc_anchors_mask_workspace(ctypes.byref(d)))
-    if ws_bytes == _BAD_SIZE:
-        raise _lib.PapcError("papc_anchors_mask_workspace: " + lib.papc_last_error_string().decode("utf-8", "replace"))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if workspace is None else workspace
-    assert ws.dtype == torch.uint8 and ws.is_cuda and ws.numel() >= ws_bytes, "workspace: %d bytes of uint8 on the device needed" % ws_bytes
+    ws, _ = _lib.workspace("papc_anchors_mask_workspace", d, dev, workspace)
     io = AnchorsMaskIo(coors=ptr(coors) if coors.shape[0] else None, cells=ptr(cells), mask=ptr(out))
     check(lib.papc_anchors_mask_u8(ctypes.byref(d), ctypes.byref(io), ptr(ws), ws.numel(), stream_ptr()), "papc_anchors_mask_u8")
     return out
@@ -288,54 +273,16 @@ def anchors_mask(coors, batch_size, cache, anchor_area_threshold=1, out=None, wo
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # second_box_encode and assign
 
-def _encode_torch(boxes, anchors, encode_angle_to_vector, smooth_dim):
-    """second_box_encode (box_np_ops.py:30-66), op for op"""
-    xa, ya, za, wa, la, ha, ra = torch.split(anchors, 1, dim=-1)
-    xg, yg, zg, wg, lg, hg, rg = torch.split(boxes, 1, dim=-1)
-    two = _const(2.0, boxes)
-    zg = zg + hg / two
-    za = za + ha / two
-    diagonal = torch.sqrt(la * la + wa * wa)
-    xt = (xg - xa) / diagonal
-    yt = (yg - ya) / diagonal
-    zt = (zg - za) / ha
-    if smooth_dim:
-        one = _const(1.0, boxes)
-        lt, wt, ht = lg / la - one, wg / wa - one, hg / ha - one
-    else:
-        lt, wt, ht = torch.log(lg / la), torch.log(wg / wa), torch.log(hg / ha)
-    if encode_angle_to_vector:
-        return torch.cat([xt, yt, zt, wt, lt, ht, torch.cos(rg) - torch.cos(ra), torch.sin(rg) - torch.sin(ra)], dim=-1)
-    return torch.cat([xt, yt, zt, wt, lt, ht, rg - ra], dim=-1)
-
-
 def second_box_encode(boxes, anchors, encode_angle_to_vector=False, smooth_dim=False, fused=None):
     """box_np_ops.py:30: boxes [..., 7] (x, y, z, w, l, h, r), anchors [..., 7] -> encodings [..., 7] ([..., 8] with encode_angle_to_vector);
-    the inverse of detect.second_box_decode."""
-    assert boxes.shape[-1] == 7 and anchors.shape[-1] == 7, "boxes [..., 7] and anchors [..., 7] expected"
-    if not _use_fused(fused):
-        return _encode_torch(boxes.float(), anchors.float().expand(boxes.shape), encode_angle_to_vector, smooth_dim)
-    if not boxes.is_cuda or not anchors.is_cuda:
-        raise _lib.PapcError("second_box_encode needs CUDA (ROCm) tensors: there is no CPU fallback (PAPC_DET_TARGETS=0 selects the torch-op flavour)")
-    code = 8 if encode_angle_to_vector else 7
-    bx = boxes.contiguous().float()
-    anc = anchors.expand(bx.shape).contiguous().float()
-    out = torch.empty(bx.shape[:-1] + (code,), dtype=torch.float32, device=bx.device)
-    n = bx.numel() // 7
-    if n:
-        check(_lib.load().papc_box_encode_f32(ptr(bx), ptr(anc), n, code, int(bool(encode_angle_to_vector)), int(bool(smooth_dim)), ptr(out),
-                                              stream_ptr()), "papc_box_encode_f32")
-    return out
+    boxcodec.second_box_encode under this module's switch."""
+    return boxcodec.second_box_encode(boxes, anchors, encode_angle_to_vector, smooth_dim, _use_fused(fused))
 
 
 def assign_workspace_bytes(B, A, Gmax, encode_angle_to_vector=False):
     """bytes of workspace one assign call of this shape needs (papc_det_assign_workspace); raises PapcError outside the kernels' limits"""
-    lib = _lib.load()
     d = DetAssignDesc(B=B, A=A, Gmax=Gmax, encode_angle_to_vector=int(bool(encode_angle_to_vector)), code_size=8 if encode_angle_to_vector else 7)
-    n = int(lib.papc_det_assign_workspace(ctypes.byref(d)))
-    if n == _BAD_SIZE:
-        raise _lib.PapcError("papc_det_assign_workspace: " + lib.papc_last_error_string().decode("utf-8", "replace"))
-    return n
+    return _lib.workspace_bytes("papc_det_assign_workspace", d)
 
 
 def _iou_torch(bv, qbv):
@@ -400,12 +347,9 @@ def assign(cache, gt_boxes, gt_classes, num_gt, anchors_mask=None, out=None, wor
         raise _lib.PapcError("assign needs CUDA (ROCm) tensors: there is no CPU fallback (PAPC_DET_TARGETS=0 selects the torch-op flavour)")
     if Gmax > GMAX_LIMIT:
         raise _lib.PapcError("assign: Gmax=%d not in [0, %d]" % (Gmax, GMAX_LIMIT))
-    res = {} if out is None else out
-    for name, dt, shape in (("labels", torch.int32, (B, A)), ("reg_targets", torch.float32, (B, A, code)), ("reg_weights", torch.float32, (B, A)),
-                            ("gt_ids", torch.int32, (B, A)), ("max_overlap", torch.float32, (B, A)), ("num_pos", torch.int32, (B,))):
-        if name not in res:
-            res[name] = torch.empty(shape, dtype=dt, device=dev)
-        assert res[name].shape == shape and res[name].dtype == dt and res[name].is_contiguous(), name
+    res = _lib.outputs({} if out is None else out,
+                       (("labels", torch.int32, (B, A)), ("reg_targets", torch.float32, (B, A, code)), ("reg_weights", torch.float32, (B, A)),
+                        ("gt_ids", torch.int32, (B, A)), ("max_overlap", torch.float32, (B, A)), ("num_pos", torch.int32, (B,))), dev)
 
     if not use_fused:
         res["labels"].fill_(-1), res["gt_ids"].fill_(-1)
@@ -423,11 +367,7 @@ def assign(cache, gt_boxes, gt_classes, num_gt, anchors_mask=None, out=None, wor
         mask = mask.contiguous() if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8).contiguous()
     lib = _lib.load()
     d = DetAssignDesc(B=B, A=A, Gmax=Gmax, encode_angle_to_vector=int(angle_vec), smooth_dim=int(smooth), code_size=code)
-    ws_bytes = int(lib.papc_det_assign_workspace(ctypes.byref(d)))
-    if ws_bytes == _BAD_SIZE:
-        raise _lib.PapcError("papc_det_assign_workspace: " + lib.papc_last_error_string().decode("utf-8", "replace"))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if workspace is None else workspace
-    assert ws.dtype == torch.uint8 and ws.is_cuda and ws.numel() >= ws_bytes, "workspace: %d bytes of uint8 on the device needed" % ws_bytes
+    ws, _ = _lib.workspace("papc_det_assign_workspace", d, dev, workspace)
     io = DetAssignIo(anchors=ptr(anchors), anchors_bv=ptr(cache["anchors_bv"]), matched=ptr(cache["matched_thresholds"]),
                      unmatched=ptr(cache["unmatched_thresholds"]), anchors_mask=ptr(mask), gt_boxes=ptr(gt_boxes) if Gmax else None,
                      gt_classes=ptr(gt_classes) if Gmax else None, num_gt=ptr(num_gt), labels=ptr(res["labels"]),

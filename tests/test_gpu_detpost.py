@@ -181,6 +181,50 @@ def test_fused_and_torch_op_legs_agree(rot):
     assert_close(a["boxes"], b["boxes"], rel=1e-6, what="legs boxes rot=%d" % rot)
 
 
+def _dense_frame(N, rot):
+    """N anchors on a jittered 13-column grid, pitched so that neighbours overlap past the threshold and second neighbours do not (the axis-aligned
+    IoU counts a "+1" per side, hence its wider pitch); zero encodings, so a decoded box is its anchor's floats exactly (0 * d + xa, expf(0) * wa,
+    0 + ra); one class column of N distinct logits in [-2, 2], at least 0.03 apart, shuffled: sigmoid gaps of 3e-3 and more, which no two
+    roundings of a sigmoid reorder.  Seed 33: no pair's IoU within 8e-4 of the threshold, 18 to 51 boxes suppressed in the four cases."""
+    rng = np.random.default_rng(33)
+    px, py, jit = (0.45, 1.2, 0.15) if rot else (0.8, 2.0, 0.3)
+    i = np.arange(N)
+    anchors = np.zeros((N, 7), np.float32)
+    anchors[:, 0] = (i % 13) * px + rng.uniform(-jit, jit, N)
+    anchors[:, 1] = (i // 13) * py + rng.uniform(-jit, jit, N)
+    anchors[:, 2] = -1.78
+    anchors[:, 3:6] = (1.6, 3.9, 1.56)
+    anchors[:, 6] = rng.uniform(-0.6, 0.6, N) if rot else 0.0
+    cls = rng.permutation(np.linspace(-2.0, 2.0, N)).astype(np.float32)[:, None]
+    return dict(box=np.zeros((N, 7), np.float32), cls=cls, dir=np.zeros((N, 2), np.float32), anchors=anchors, mask=None)
+
+
+@pytest.mark.parametrize("N", [65, 130])
+@pytest.mark.parametrize("rot", [True, False])
+def test_suppression_agrees_with_the_standalone_nms(rot, N):
+    """predict()'s suppression and nms.rotate_nms_gpu_tensor / nms.nms_gpu_tensor run one tile and one sweep (csrc/nms_iou.h): on the same boxes
+    and scores they keep the same anchors in the same order.  N = 65 and 130: two and three column blocks, a partial last one, off-diagonal
+    tiles on both sides of a block edge.  With r = 0 the stand-up box is exactly (x - w/2, y - l/2, x + w/2, y + l/2): cos 0 = 1 and
+    sin 0 = 0 leave each corner term exact."""
+    from papc_amd import detect, nms
+    fr = _dense_frame(N, rot)
+    cfg = dict(D.CFG, rotate=rot, score_thresh=0.0, pre_max=N, post_max=N, use_dir=False)
+    cls = torch.from_numpy(fr["cls"][None]).cuda()
+    anchors = torch.from_numpy(fr["anchors"]).cuda()
+    r = detect.predict_tensors(torch.from_numpy(fr["box"][None]).cuda(), cls, None, anchors, None, fused=True, **_kw(cfg, 1))
+    n = int(r["num_det"][0])
+    x, y, w, l, ang = (anchors[:, k] for k in (0, 1, 3, 4, 6))
+    score = torch.sigmoid(cls[0, :, 0])
+    if rot:
+        keep = nms.rotate_nms_gpu_tensor(torch.stack([x, y, w, l, ang, score], dim=1), cfg["iou_thresh"])
+    else:
+        keep = nms.nms_gpu_tensor(torch.stack([x - w / 2, y - l / 2, x + w / 2, y + l / 2, score], dim=1), cfg["iou_thresh"])
+    print("[nms agreement] rot=%d N=%d kept %d suppressed %d" % (rot, N, n, N - n))
+    assert n >= N / 8 and N - n >= N / 8                                                       # neither side of the decision is vacuous
+    assert int(r["num_pass"][0]) == N
+    assert r["anchor_idx"][0, :n].tolist() == keep.tolist()
+
+
 def test_predict_dict_interface_on_rpn_maps():
     """predict() on the RPN's [B,H,W,.] maps: the source's list of dicts, None entries for the frame without a detection"""
     from papc_amd import detect
