@@ -155,8 +155,8 @@ __device__ __forceinline__ void prep_consts(const PrepArgs &p, int cb, float (*c
     __syncthreads();
 }
 
-// grid (channel blocks of 32, row blocks of 128); a wave owns one 32 x 32 tile
-template <int MODE>
+// grid (channel blocks of 32, row blocks of 128); a wave owns one 32 x 32 tile.  RAGGED: transposed planes of M % 128 != 0 rows
+template <int MODE, bool RAGGED = false>
 __global__ __launch_bounds__(256) void pg_prep_kernel(PrepArgs p)
 {
     __shared__ float tile[4][32][33];
@@ -245,12 +245,15 @@ __global__ __launch_bounds__(256) void pg_prep_kernel(PrepArgs p)
 #pragma unroll
             for (int i = 0; i < 8; ++i) tile[wv][r_in][16 * j + 8 * h + i] = v[j][i];
         __syncthreads();
+        // (a channel's row of PT holds KBt = ru(M, 32) / 16 k blocks: a wave whose 32 rows lie behind M -- the row block is 128 -- has none)
+        if (!RAGGED || (int64_t)mb * 32 < p.M) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            float u[8];
+            for (int j = 0; j < 2; ++j) {
+                float u[8];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) u[i] = tile[wv][16 * j + 8 * h + i][r_in];
-            store_planes8(p.PT + ((int64_t)cb * p.KBt + mb * 2 + j) * 3072, lane, u);
+                for (int i = 0; i < 8; ++i) u[i] = tile[wv][16 * j + 8 * h + i][r_in];
+                store_planes8(p.PT + ((int64_t)cb * p.KBt + mb * 2 + j) * 3072, lane, u);
+            }
         }
     }
 }
@@ -816,13 +819,20 @@ int papc_pg_prep_rows_f32(const papc_pg_prep *a, papc_stream_t stream)
     hipStream_t st = as_stream(stream);
     ProfScope prof(PAPC_K_MISC, st);
     const dim3 grid((unsigned)(ru64(a->C, 32) / 32), (unsigned)(ru64(a->M, 128) / 128));
+    const bool ragged = a->planes_t && a->M % 128 != 0;    // (the last row block has waves behind M: they must not store into planes_t)
+#define PG_PREP_GO(MODE_)                                                                                  \
+    do {                                                                                                   \
+        if (ragged) hipLaunchKernelGGL((pg_prep_kernel<MODE_, true>), grid, dim3(256), 0, st, p);          \
+        else hipLaunchKernelGGL((pg_prep_kernel<MODE_, false>), grid, dim3(256), 0, st, p);                \
+    } while (0)
     switch (mode) {
-    case PG_PREP_PLAIN: hipLaunchKernelGGL(pg_prep_kernel<PG_PREP_PLAIN>, grid, dim3(256), 0, st, p); break;
-    case PG_PREP_CONCAT: hipLaunchKernelGGL(pg_prep_kernel<PG_PREP_CONCAT>, grid, dim3(256), 0, st, p); break;
-    case PG_PREP_BNRELU: hipLaunchKernelGGL(pg_prep_kernel<PG_PREP_BNRELU>, grid, dim3(256), 0, st, p); break;
-    case PG_PREP_DY_DENSE: hipLaunchKernelGGL(pg_prep_kernel<PG_PREP_DY_DENSE>, grid, dim3(256), 0, st, p); break;
-    default: hipLaunchKernelGGL(pg_prep_kernel<PG_PREP_DY_MAX>, grid, dim3(256), 0, st, p); break;
+    case PG_PREP_PLAIN: PG_PREP_GO(PG_PREP_PLAIN); break;
+    case PG_PREP_CONCAT: PG_PREP_GO(PG_PREP_CONCAT); break;
+    case PG_PREP_BNRELU: PG_PREP_GO(PG_PREP_BNRELU); break;
+    case PG_PREP_DY_DENSE: PG_PREP_GO(PG_PREP_DY_DENSE); break;
+    default: PG_PREP_GO(PG_PREP_DY_MAX); break;
     }
+#undef PG_PREP_GO
     return check_launch("papc_pg_prep_rows_f32");
 }
 
