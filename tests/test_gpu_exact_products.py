@@ -52,13 +52,22 @@ not tell kernels of one family apart, so launch counts are not used).
   smallm.hip:489     (k16 ring)  test_planes, PAPC_PG_PIPE=1 (papc_pg_gemm_f32:885), NB 1 and 2, and pg_gemm_group_kernel<.., true>
   smallm.hip:609     (k32 stage loop)  test_planes, PAPC_PG_PIPE=0, and PAPC_PG_NS=3 under either value
   cloud_concat_k.hip:113   test_cloud_concat_k_forward (tier 2)
-  kdlevel.h:50       test_kdconv_forward (tier 2; kd_step also serves kd_dx_acc, not probed)
-  kdlevel.h:263      (kd_dw_acc)  NOT probed yet: papc_kdconv_bwd_f32 can be made exact (positive operands), the case is not built
-  voxconv.hip:58     test_voxconv1_forward (tier 2; vox_step is the one product of all five voxconv kernels -- voxconv2_pool_fwd / _bwd_dx / _bwd_dw and
-                     voxconv1_bwd_dw reach it through loaders of their own, which are not probed yet)
+  kdlevel.h:50       (kd_step)  test_kdconv_forward (tier 2), through kd_fwd_acc
+  kdlevel.h:263      (kd_dw_acc, which splits its own operands)  test_gpu_exact_loaders.py::test_kdconv_bwd_dw, see below
+  voxconv.hip:58     (vox_step, the one product of all five voxconv kernels)  test_voxconv1_forward (tier 2), through vox_conv1_fwd_kernel's loader
   pfn.hip:404        test_pfn_apply (tier 2): k = 2, 3 as single terms, k = 0 + 7 and 1 + 8 as two equal terms; columns 4 - 6 (xyz - mean) cannot carry
                      an exact non-zero value
-  kdbn (kdbn.hip) always normalises its accumulator: no exact image.
+The six loaders that reach kd_step / vox_step / mfma_bf16x3 through a k loop and an on-load operand selection of their own -- each a separately
+compiled kernel -- have their cases in the sibling file tests/test_gpu_exact_loaders.py (its docstring has the operand layouts):
+  voxconv.hip:149    (vox_conv2_pool_kernel)  test_voxconv2_pool_forward: the one kernel of papc_voxconv2_pool_fwd_f32; (B, E) = (3, 15), (1, 19)
+  voxconv.hip:231    (vox_conv2_dx_kernel, with vox_gp_kernel)  test_voxconv2_bwd_dx: the two launches of papc_voxconv2_bwd_dx_f32; E = 19, B = 4
+  voxconv.hip:289    (vox_conv2_dw_kernel, its fold, vox_db2_kernel)  test_voxconv2_bwd_dw: papc_voxconv2_bwd_dw_f32; two chunks of VX_DWG = 64 groups
+  voxconv.hip:332    (vox_conv1_dw_kernel and its fold)  test_voxconv1_bwd_dw: papc_voxconv1_bwd_dw_f32; three chunks of VX_W1CH = 256 rows and one of 96
+  kdlevel.h:135      (kd_dx_kernel / kd_dx_acc on kd_step)  test_kdconv_bwd_dx: papc_kdconv_bwd_f32 with dx given, Cin >= 32 (kdconv.hip:184-188)
+  kdlevel.h:207      (kd_dw_kernel / kd_dw_acc<1>, papc_reduce_partials2_f32)  test_kdconv_bwd_dw: papc_kdconv_bwd_f32, Cin >= 32 (kdconv.hip:197-202)
+  (papc_voxconv2_prep_f32, which every conv2 case reads its weights through: test_voxconv2_prep and an assertion in each case)
+What stays out: kdbn (kdbn.hip) always normalises its accumulator -- no exact image; the Cin = 3 kernels (kd_fwd3 / kd_dx3 / kd_dw3) are fmaf chains on
+the vector unit, not MFMA loops.
 
 Also pinned here: papc_pg_prep_rows_f32 writes planes_t for M % 128 != 0 inside its buffer (the planes_t cases have M = 32 and 64; before this
 file the waves of a 128-row block behind M wrote zeros past a channel's k blocks and past the buffer).
@@ -66,6 +75,9 @@ file the waves of a 128-row block behind M wrote zeros past a channel's k blocks
 Measured on the MI355X (every case, one run): 0 of N outputs differ in every family -- tiled forward 16 x 426 000 + 8 x 213 000 outputs,
 row-streaming forward 13 cases (65 536 .. 262 144 each), tiled dX 24 cases (58 240 .. 878 080), streaming dX 32, compacted dX 3 x 32 768, dW 26
 cases (1 092 .. 200 704), dW max 8 192 + 12 352, planes 12 cases (65 536 .. 278 528), cloud concat 3, kd conv 2, vox conv1 2, pfn apply 2.
+The loaders (tests/test_gpu_exact_loaders.py, one run): 0 of N outputs differ in every family -- vox conv2 + pool forward 768 and 864 outputs (and every
+winner byte), vox conv2 dX 2 x 68 992 (3 456 of gp, 65 536 of dz), vox conv2 dW 2 x 27 680 (27 648 + db2), vox conv1 dW 2 x 4 032 (4 000 + db1),
+kd conv dX 3 200 and 9 600, kd conv dW 3 168 and 46 560 (dW + dbias); wk / wt equal the transposes in all five launches of the prep kernel.
 
 What a broken loop does to this file was tried once, on a scratch build that is not in the tree: product 0 dropped at mlp_gemm.hip:304, planes
 1 / 2 swapped in mlp_stream.hip's weight image, product 0 issued twice in smallm.hip's k16 ring, and pl[1] / pl[2] swapped in split8 (which
@@ -73,6 +85,12 @@ reached the sources rebuilt against that bf16x3.h: the dW rows / rowsx / max ker
 in the file failed: every bf16x3 case of the tiled, row-streaming, compacted and planes kernels and of the split8-fed dW kernels.  The 41 that
 passed: the true-fp32 flavours (f32 = 1), the dW cases that run dw_ws_kernel / dw_kernel under every knob, the refusals, and cloud_concat_k /
 kdconv, whose objects were not rebuilt.
+
+The same for the loaders, on a second scratch build loaded through PAPC_LIB: planes 1 / 2 of the A operand exchanged in vox_step, and product 0
+(a3 b1) left out of a local copy of the product loop in kd_dw_acc.  10 of the 13 tests of tests/test_gpu_exact_loaders.py failed: every case of the four
+voxconv loaders (pool forward 768 of 768 and 864 of 864 outputs, dX 17 280 of 65 536 -- every non-zero element of dz --, conv2 dW 27 648 of 27 648,
+conv1 dW 4 000 of 4 000) and both kd dW cases (3 072 of 3 072, 46 080 of 46 080).  The 3 that passed: test_voxconv2_prep (a copy), and the two kd dX
+cases, which run kd_step, left intact.  Within the failing cases gp, db2, db1 and dbias still agreed: none of them passes through an MFMA.
 """
 import ctypes
 
