@@ -906,6 +906,58 @@ int papc_leaky_dropout_bwd_f32(const float *gout, const float *x, const uint8_t 
  * clamped and counted in err [1]. */
 int papc_occupancy_grid_f32(const float *points, int B, int N, int E, float *grid, uint32_t *err, papc_stream_t stream);
 
+/* ---- PointPillars RPN: implicit-GEMM 2-D convolutions (conv2d.hip) ----------------------------- */
+/* The convolutions of PAPC/models/detect/pointpillars/models/bones/rpn.py:71-133: Pad2D(1) + Conv2D(3, stride s) / Conv2D(3, padding=1) without bias
+ * (in [B, H, W] -> out [B, Ho, Wo], Ho = (H - 1) / s + 1) and Conv2DTranspose(kernel = stride = s) (out [B, s H, s W]), each under a BatchNorm + ReLU
+ * that the CONSUMER applies on load.  Activations are channel-last rows [B H W, C] of the PRE-norm conv output; w [Cout, Cin, 3, 3] and the
+ * deconvolution's [Cin, Cout, s, s] are the source's shapes.  All products bf16x3 MFMA (fp32 accuracy), no atomics, fixed-order folds.
+ *   conv2d_ok / deconv2d_ok   != 0 where the kernels take the layer: Cin, Cout multiples of 32 up to 256, stride 1 or 2 (deconv: 1, 2 or 4), H, W >= 1.
+ *                        The calls below return PAPC_E_UNSUPPORTED elsewhere.
+ *   conv2d_parts         rows of a partial buffer over M pixel rows: ceil(M / 128).
+ *   conv2d_prep          for `count` <= 32 layers in one launch (HOST arrays, read during the call): wk / wt [Cin Cout taps] each, the K-major orders
+ *                        the calls below read (conv: wk [co][tap][ci], wt [ci][tap][co]; deconv: wk [ij][co][ci], wt [ci][ij][co]).
+ *   conv2d_fwd           y [B Ho Wo, Cout] = conv(a), a = x [B H W, Cin] (scale_in == NULL) or relu(scale_in x + shift_in) with the exact-zero halo;
+ *                        stats_partial [conv2d_parts(B Ho Wo), 2, Cout] = per-workgroup (sum y, sum y^2): feed papc_bn_finalize_f32 with M = B Ho Wo.
+ *   conv2d_bwd_dx        dY = scale (dz - c1 - xhat c2) on load from dz, y [B Ho Wo, Cout] and the layer's constants (c1, c2 from
+ *                        papc_bn_bwd_finalize_f32); dx [B H W, Cin] = (conv^T dY + addend) and, with y_prev [B H W, Cin] and its constants, x ReLU'
+ *                        (sign of scale_prev y_prev + shift_prev) with red_partial [conv2d_parts(B H W), 2, Cin] = (sum dx, sum dx xhat_prev).
+ *                        addend, y_prev (and red_partial with it) may be NULL.
+ *   conv2d_bwd_dw        dw [Cout, Cin, 3, 3], written or (accumulate) added; x, scale_in, shift_in as in conv2d_fwd.
+ *   deconv2d_fwd         y [b, s h + i, s w + j, coff + co] of a buffer with ldy floats per pixel; stats_partial [conv2d_parts(B H W) s^2, 2, Cout], M = B H W s^2.
+ *   deconv2d_bwd_dx / _dw     the same from dz, y with ld floats per pixel at column coff; dw [Cin, Cout, s, s].
+ *   conv2d_relu_bwd      over the C columns at coff of buffers with ld floats per row: dz = gout [scale y + shift > 0] and red_partial
+ *                        [conv2d_relu_bwd_parts(M), 2, C] = (sum dz, sum dz xhat): the backward entry of a buffer whose activated copy went to
+ *                        another consumer.  dz must not alias gout.
+ * Every activation, weight order and constant vector 16-byte aligned; ld, coff multiples of 4. */
+int papc_conv2d_ok(int Cin, int Cout, int stride, int H, int W);
+int papc_deconv2d_ok(int Cin, int Cout, int stride);
+int papc_conv2d_parts(int64_t M);
+int papc_conv2d_prep_f32(const float *const *w, float *const *wk, float *const *wt, const int *cin, const int *cout, const int *stride, const int *deconv,
+                         int count, papc_stream_t stream);
+int papc_conv2d_fwd_f32(const float *x, const float *scale_in, const float *shift_in, const float *wk, int B, int H, int W, int Cin, int Cout, int stride,
+                        float *y, float *stats_partial, papc_stream_t stream);
+int papc_conv2d_bwd_dx_f32(const float *dz, const float *y, const float *mean, const float *invstd, const float *scale, const float *c1, const float *c2,
+                           const float *wt, int B, int H, int W, int Cin, int Cout, int stride, const float *addend, const float *y_prev,
+                           const float *mean_prev, const float *invstd_prev, const float *scale_prev, const float *shift_prev, float *dx,
+                           float *red_partial, papc_stream_t stream);
+size_t papc_conv2d_bwd_dw_workspace(int B, int H, int W, int Cin, int Cout, int stride);
+int papc_conv2d_bwd_dw_f32(const float *dz, const float *y, const float *mean, const float *invstd, const float *scale, const float *c1, const float *c2,
+                           const float *x, const float *scale_in, const float *shift_in, int B, int H, int W, int Cin, int Cout, int stride, float *dw,
+                           int accumulate, void *workspace, size_t workspace_bytes, papc_stream_t stream);
+int papc_deconv2d_fwd_f32(const float *x, const float *scale_in, const float *shift_in, const float *wk, int B, int H, int W, int Cin, int Cout, int stride,
+                          float *y, int64_t ldy, int coff, float *stats_partial, papc_stream_t stream);
+int papc_deconv2d_bwd_dx_f32(const float *dz, const float *y, int64_t ld, int coff, const float *mean, const float *invstd, const float *scale,
+                             const float *c1, const float *c2, const float *wt, int B, int H, int W, int Cin, int Cout, int stride, const float *addend,
+                             const float *y_prev, const float *mean_prev, const float *invstd_prev, const float *scale_prev, const float *shift_prev,
+                             float *dx, float *red_partial, papc_stream_t stream);
+size_t papc_deconv2d_bwd_dw_workspace(int B, int H, int W, int Cin, int Cout, int stride);
+int papc_deconv2d_bwd_dw_f32(const float *dz, const float *y, int64_t ld, int coff, const float *mean, const float *invstd, const float *scale,
+                             const float *c1, const float *c2, const float *x, const float *scale_in, const float *shift_in, int B, int H, int W, int Cin,
+                             int Cout, int stride, float *dw, int accumulate, void *workspace, size_t workspace_bytes, papc_stream_t stream);
+int papc_conv2d_relu_bwd_parts(int64_t M);
+int papc_conv2d_relu_bwd_f32(const float *gout, const float *y, int64_t ld, int coff, const float *mean, const float *invstd, const float *scale,
+                             const float *shift, int64_t M, int C, float *dz, float *red_partial, papc_stream_t stream);
+
 /* Axis-aligned bitmask NMS: nms_gpu of pointpillars/libs/ops/non_max_suppression/nms_gpu.py:130-164 (CUDA twin
  * libs/ops/cc/nms/nms_kernel.cu.cc:38-157), all on the device.  dets [N,5] = (x1, y1, x2, y2, score) fp32, N <= 65536.
  * keep [N] int32 receives the ORIGINAL indices of the kept boxes in descending-score order (ties: higher index first, the

@@ -22,6 +22,10 @@ Public surface mirrors the reference:
                           whole batch as one launch sequence, counts on the device
   papc_amd.targets     <- the target half of prep_pointcloud (data/preprocess.py:251-302): the anchor generators, TargetAssigner, the occupied-area
                           anchor mask and assign() (create_target_np on the nearest-BEV IoU, second_box_encode) for a whole batch on the device
+  papc_amd.rpn         <- RPN (pointpillars/models/bones/rpn.py): the dense 2-D backbone as implicit-GEMM 3x3 convolutions and kernel = stride
+                          deconvolutions with the norm and ReLU applied on load, one autograd node from the canvas to the activated concat rows,
+                          the three heads one fused row GEMM
+  papc_amd.detector    <- PointPillars (detectors/pointpillars.py): PillarFeatureNet -> PointPillarsScatter -> RPN -> the loss or predict()
   papc_amd.datasets    <- PAPC/datasets loaders: PNClasDataLoader / PNSegDataLoader / KDClasDataLoader / KDSegDataLoader / VoxDataLoader
 The compute lives in libpapc_hip.so (hand-written HIP, C ABI in include/papc_hip.h).
 """

@@ -193,6 +193,20 @@ SIGNATURES = {
     "papc_voxconv2_bwd_dw_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_p, ctypes.c_size_t, c_p]),
     "papc_voxconv1_bwd_dw_workspace": (ctypes.c_size_t, [c_i, c_i]),
     "papc_voxconv1_bwd_dw_f32": (c_i, [c_p] * 8 + [c_i, c_i, c_p, c_p, c_i, c_p, ctypes.c_size_t, c_p]),
+    "papc_conv2d_ok": (c_i, [c_i] * 5),
+    "papc_deconv2d_ok": (c_i, [c_i] * 3),
+    "papc_conv2d_parts": (c_i, [c_l]),
+    "papc_conv2d_prep_f32": (c_i, [c_p] * 7 + [c_i, c_p]),
+    "papc_conv2d_fwd_f32": (c_i, [c_p] * 4 + [c_i] * 6 + [c_p, c_p, c_p]),
+    "papc_conv2d_bwd_dx_f32": (c_i, [c_p] * 8 + [c_i] * 6 + [c_p] * 9),
+    "papc_conv2d_bwd_dw_workspace": (ctypes.c_size_t, [c_i] * 6),
+    "papc_conv2d_bwd_dw_f32": (c_i, [c_p] * 10 + [c_i] * 6 + [c_p, c_i, c_p, ctypes.c_size_t, c_p]),
+    "papc_deconv2d_fwd_f32": (c_i, [c_p] * 4 + [c_i] * 6 + [c_p, c_l, c_i, c_p, c_p]),
+    "papc_deconv2d_bwd_dx_f32": (c_i, [c_p, c_p, c_l, c_i] + [c_p] * 6 + [c_i] * 6 + [c_p] * 9),
+    "papc_deconv2d_bwd_dw_workspace": (ctypes.c_size_t, [c_i] * 6),
+    "papc_deconv2d_bwd_dw_f32": (c_i, [c_p, c_p, c_l, c_i] + [c_p] * 8 + [c_i] * 6 + [c_p, c_i, c_p, ctypes.c_size_t, c_p]),
+    "papc_conv2d_relu_bwd_parts": (c_i, [c_l]),
+    "papc_conv2d_relu_bwd_f32": (c_i, [c_p, c_p, c_l, c_i] + [c_p] * 4 + [c_l, c_i, c_p, c_p, c_p]),
     "papc_leaky_dropout_fwd_f32": (c_i, [c_p, c_l, c_f, c_f, c_p, c_i, c_i, c_p, c_p, c_p]),
     "papc_leaky_dropout_bwd_f32": (c_i, [c_p, c_p, c_p, c_l, c_f, c_f, c_p, c_p]),
     "papc_occupancy_grid_f32": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
